@@ -14,9 +14,12 @@ data-path collective) and the result blocks are all-gathered over RCCL (``bl_gat
 behind the C-ABI) inside the timed region.  ESS is computed afterwards with the NumPyro estimator
 (mean over sites of per-site ESS of psi).
 
-The default run (--gpus 1, workload occu) also carries a ``secondary`` array: BASELINE.json configs[3] (occu_rn), the SURVEY
-section 8 row f3 workload (occu with site random effects) and the stacked-period stand-in of configs[4] (no reference
-counterpart), each a few steps with its own ``roofline`` and a bounded-sample ``cpu_baseline`` (``--no-secondary`` skips them).
+A plain run does only what the headline figure needs: set up, W untimed steps, K timed steps, ESS, the result line
+(and ``--dump-outputs DIR``: the last timed step's result arrays as DIR/<name>.npy).  ``--full`` adds everything else,
+after the timed region: the end-to-end ``fit()`` clock, the CPU baseline, the live PMC passes, the verbose record file,
+and (--gpus 1, workload occu) a ``secondary`` array: BASELINE.json configs[3] (occu_rn), the SURVEY section 8 row f3
+workload (occu with site random effects) and the stacked-period stand-in of configs[4] (no reference counterpart), each a
+few steps with its own ``roofline`` and a bounded-sample ``cpu_baseline`` (``--no-secondary`` skips them).
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment: this process is only a LAUNCHER.  It starts N
 fresh child processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, one per GPU) before importing torch or
@@ -93,6 +96,12 @@ TRANS_PER_CU_PER_S = 32 * 2.4e9
 # the default run, so the line quotes the committed record and keeps the live scaled estimate beside it
 RN_CPU_MEASURED = "profiles/r05/e_cpu_baseline_rn.json"
 N_CUS = 256
+# ESS(psi) of a 10k-site step costs about a second of host time on one thread (a third of that on ESS_WORKERS_MAX): it is computed
+# for at most this many timed steps, spread evenly over the run (the first and the last included), and their mean stands for every
+# step; a run of this many steps or fewer evaluates each of them, as before
+ESS_STEPS_MAX = 40
+ESS_WORKERS_MAX = 8
+DUMP_LIMIT_BYTES = 63 * 10 ** 6   # --dump-outputs: under 64 MB in all, the .npy headers included
 
 
 COMPACT_LIMIT = 4096   # bytes: the driver keeps an 8 KB tail of stdout; BENCH_r05 lost its 19.5 KB line to that
@@ -186,6 +195,11 @@ def parse_args(argv=None):
     ap.add_argument("--full-out", default=None,
                     help="where the verbose record goes (default gpurun_out/bench_full[_<workload>].json); stdout's last line is the compact one")
     ap.add_argument("--full-line", action="store_true", help="print the verbose record as the one stdout line (tools/; not what the driver reads)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the end-to-end fit() timing, the CPU baseline, the live PMC passes, the secondary "
+                         "workloads and the verbose record file (a plain run does none of these; the --no-* flags trim --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result arrays (draws, diverging, num_steps, ...) as DIR/<name>.npy, float32 or float64")
     return ap.parse_args(argv)
 
 
@@ -323,16 +337,64 @@ def psi_draws(draws, X, site="psi", effects=None):
     return (np.exp(eta) if site == "abundance" else 1.0 / (1.0 + np.exp(-eta))).astype(np.float32)
 
 
-def ess_of_site_function(draws, X, site="psi", chunk=1000, o_u=None):
+def ess_of_site_function(draws, X, site="psi", chunk=1000, o_u=None, workers=1):
     """Mean over sites of ESS(psi_i) (or abundance_i), computed over site chunks so that the (chains, draws, sites)
-    array of the deterministic site never exists as a whole (8 GPUs x 4 chains x 1000 draws x 10 000 sites)."""
+    array of the deterministic site never exists as a whole (8 GPUs x 4 chains x 1000 draws x 10 000 sites).  `workers` > 1
+    evaluates the chunks on that many threads; the chunk sums are added in site order either way (the same float)."""
+    from concurrent.futures import ThreadPoolExecutor
+
     from biolith_amd.evaluation import effective_sample_size
 
-    total, n = 0.0, X.shape[0]
-    for s0 in range(0, n, chunk):
+    n = X.shape[0]
+
+    def chunk_sum(s0):
         eff = None if o_u is None else draws[..., o_u + s0: o_u + min(s0 + chunk, n)]   # random effects: psi_i carries site_re_occ_i
-        total += float(effective_sample_size(psi_draws(draws, X[s0:s0 + chunk], site, eff)).sum())
+        return float(effective_sample_size(psi_draws(draws, X[s0:s0 + chunk], site, eff)).sum())
+
+    if workers > 1:
+        with ThreadPoolExecutor(max_workers=workers) as ex:
+            sums = list(ex.map(chunk_sum, range(0, n, chunk)))
+    else:
+        sums = [chunk_sum(s0) for s0 in range(0, n, chunk)]
+    total = 0.0
+    for s in sums:
+        total += s
     return total / n
+
+
+def host_workers():
+    """Threads for host-side number crunching: the CPUs this process may run on, at most ESS_WORKERS_MAX."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    return max(1, min(ESS_WORKERS_MAX, n))
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: every array as path/<name>.npy, float32 kept, any other dtype as float64.  At most `limit` bytes in all: an
+    array over its share keeps a fixed, seeded sample of its last axis, and the kept indices go beside it as <name>_index.npy."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: (v if v.dtype == np.float32 else v.astype(np.float64)) for k, v in arrays.items()}
+    left, written = int(limit), {}
+    order = sorted(arrays, key=lambda k: arrays[k].nbytes)
+    for i, name in enumerate(order):
+        a = arrays[name]
+        share = left // (len(order) - i)
+        if a.nbytes > share and a.ndim >= 1 and a.shape[-1] > 1:
+            col = a.nbytes // a.shape[-1]                       # bytes of one index of the last axis, + 8 for the index itself
+            keep = max(1, min(a.shape[-1], share // (col + 8)))
+            idx = np.sort(np.random.default_rng(seed).choice(a.shape[-1], size=keep, replace=False))
+            a = np.ascontiguousarray(a[..., idx])
+            np.save(os.path.join(path, f"{name}_index.npy"), idx.astype(np.float64))
+            left -= idx.size * 8
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        left -= a.nbytes
+        written[name] = list(a.shape)
+    return written
 
 
 def cpu_baseline(data, threads, wl, chains=CHAINS_PER_GPU):
@@ -727,14 +789,18 @@ def main(argv=None):
             return None, None, None
 
         # ---- metric numerator: ESS(psi), NumPyro estimator, mean over sites (diagnostics.py:28-32) ----
+        # (at most ESS_STEPS_MAX steps evaluated, evenly spread; with more timed steps their mean stands for every step)
+        ess_at = sorted({int(round(x)) for x in np.linspace(0, n_steps - 1, min(n_steps, ESS_STEPS_MAX))})
         ess_psi, ess_coef, rhat = [], [], []
-        for _, d in steps:
+        for i, (_, d) in enumerate(steps):
             G0 = ds.Ks + ds.Ko + 2
             fixed = d[..., :G0] if wl["model"] == "occu_re" else d   # (with random effects: min ESS / R-hat over the fixed effects)
-            ess_psi.append(ess_of_site_function(d.astype(np.float64), X, wl["site"], o_u=G0 + 1 if wl["model"] == "occu_re" else None))
+            if i in ess_at:
+                ess_psi.append(ess_of_site_function(d.astype(np.float64), X, wl["site"], o_u=G0 + 1 if wl["model"] == "occu_re" else None,
+                                                    workers=host_workers()))
             ess_coef.append(effective_sample_size(fixed).min())
             rhat.append(float(split_gelman_rubin(fixed).max()))
-        total_ess = float(np.sum(ess_psi))
+        total_ess = float(np.sum(ess_psi)) if len(ess_psi) == n_steps else float(np.mean(ess_psi)) * n_steps
         N, T, J, Ks, Ko = ds.N, ds.T, ds.J, ds.Ks, ds.Ko
         bytes_eval = algorithmic_bytes_per_eval(N, T, J, Ks, Ko)
         if wl["model"] == "occu_re":   # + the sampler's own vectors: about 14 of them are read or written per leapfrog
@@ -752,7 +818,7 @@ def main(argv=None):
             if ent:
                 traffic = ent.get("hbm_bytes_per_launch")
                 traffic_source = f"profiles/pmc_traffic.json (static; from {ent.get('source')})"
-        if world == 1 and not args.no_live_pmc:
+        if world == 1 and args.full and not args.no_live_pmc:
             # measured NOW (two --pmc passes over a child process, after this workload's timed region; a few seconds each); the
             # committed figure stays as the fallback and is quoted beside it
             try:
@@ -866,20 +932,28 @@ def main(argv=None):
                 "step_size": [float(x) for x in steps[-1][0].step_size], "mean_accept_prob": float(steps[-1][0].accept_prob.mean()),
                 "leapfrogs_per_s_per_chain": 1e3 * (leap_mean / NCH) / kernel_ms_mean,
             },
-            "ess": {f"{wl['site']}_mean_over_sites_per_step": ess_psi, "min_coef_per_step": [float(x) for x in ess_coef],
+            "ess": {f"{wl['site']}_mean_over_sites_per_step": ess_psi, "steps_evaluated": ess_at, "min_coef_per_step": [float(x) for x in ess_coef],
                     "max_split_rhat": max(rhat), "draws_per_step": NCH * world * NUM_SAMPLES},
         }
         # what the scaled CPU baseline of a secondary workload needs: posterior draws to evaluate at, and the launch's size
-        aux = dict(data=data, X=X, draws=steps[-1][1], leap_per_step=leap_mean, ess_per_step=total_ess / n_steps, D=ds.D, chains=NCH)
+        aux = dict(data=data, X=X, draws=steps[-1][1], leap_per_step=leap_mean, ess_per_step=total_ess / n_steps, D=ds.D, chains=NCH,
+                   last=steps[-1][0])
         if gather_hung[0]:
             kept_alive.append(ds)   # the abandoned worker thread still refers to it (its events must outlive the thread): kept until exit
         del ds
         return out, aux, wl
 
     out, aux, wl = bench_workload(args.workload, args.steps, args.warmup)
+    if rank == 0 and args.dump_outputs:
+        # what the timed path handed its caller in the last timed step (rank 0's chains; with several ranks also the gathered draws)
+        last = aux["last"]
+        arrays = {nm: getattr(last, nm) for nm in GATHERED}
+        if world > 1 and aux["draws"] is not None:
+            arrays["draws_all_ranks"] = aux["draws"]
+        dump_outputs(args.dump_outputs, arrays)
     if rank == 0:
         # Everything below runs AFTER the measured line exists: a failure in a late leg is recorded in the line, never loses it.
-        if world == 1 and args.workload == "occu" and not args.no_e2e:
+        if world == 1 and args.full and args.workload == "occu" and not args.no_e2e:
             try:
                 # SURVEY section 8d's second clock: end-to-end fit() from host arrays, PCIe and the psi fetch included (never `value`)
                 runs = fit_end_to_end(aux["data"], chains=aux["chains"])
@@ -896,7 +970,7 @@ def main(argv=None):
                                           "as biolith/benchmarks/occu_spoccupancy.py:104-113 times it; library already loaded"}
             except Exception as exc:  # noqa: BLE001
                 out["fit_e2e_error"] = f"{type(exc).__name__}: {exc}"
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 threads = min(aux["chains"], os.cpu_count() or 1)
                 if args.workload in ("occu", "occu_cfg1") or args.cpu_baseline:   # the oracle's own sampler run (the headline: the same chains x draws as the GPU)
@@ -914,7 +988,7 @@ def main(argv=None):
             except Exception as exc:  # noqa: BLE001
                 out["cpu_baseline_error"] = f"{type(exc).__name__}: {exc}"
     aux = None
-    if world == 1 and args.workload == "occu" and not args.no_secondary and rank == 0:
+    if world == 1 and args.full and args.workload == "occu" and not args.no_secondary and rank == 0:
         # ---- the other workloads of SURVEY section 8 in the same driver-run line (only the headline was driver-measured) ----
         out["secondary"] = []
         for name, k_steps, k_warm in SECONDARY:
@@ -954,7 +1028,7 @@ def main(argv=None):
                                  (round(e["cpu_baseline"]["value"], 2) if "cpu_baseline" in e else None)]
                                 if "error" not in e else "error") for e in out["secondary"]}
         full_path = args.full_out or os.path.join(ROOT, "gpurun_out", "bench_full.json" if args.workload == "occu" else f"bench_full_{args.workload}.json")
-        wrote = write_full_record(out, full_path)
+        wrote = write_full_record(out, full_path) if args.full or args.full_out else None   # (a plain run writes no record)
         sys.stdout.flush()
         print(json.dumps(out) if args.full_line else compact_line(out, wrote), flush=True)
     if comm is not None:

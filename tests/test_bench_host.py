@@ -109,3 +109,43 @@ def test_rn_roofline_peak_and_executed_terms():
     assert ex == items * 8 * J and N <= items <= N * 13 and ex < N * J * 101
     cb = bench.committed_cpu_baseline(bench.RN_CPU_MEASURED)
     assert cb["scaled"] is False and cb["kind"] == "port" and cb["value"] > 0 and "NOT timed in this run" in cb["sample"]
+
+
+def test_plain_run_flags():
+    """A plain run leaves the extra legs to --full; --dump-outputs names a directory."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_ess_of_site_function_threads_give_the_same_float():
+    rng = np.random.default_rng(1)
+    X = rng.normal(size=(2500, 3))
+    d = rng.normal(size=(4, 200, 8)) * 0.2
+    one = bench.ess_of_site_function(d, X, "psi", chunk=500)
+    assert bench.ess_of_site_function(d, X, "psi", chunk=500, workers=4) == one
+    assert 0 < one <= 4 * 200 * 4      # (antithetic chains may exceed the draw count, never by much)
+
+
+def test_dump_outputs_dtypes_and_size_cap(tmp_path):
+    rng = np.random.default_rng(2)
+    arrays = dict(draws=rng.normal(size=(4, 100, 500)).astype(np.float32), num_steps=rng.integers(1, 64, size=(4, 100)).astype(np.int32),
+                  diverging=np.zeros((4, 100), dtype=bool), step_size=np.ones(4, dtype=np.float64))
+    shapes = bench.dump_outputs(str(tmp_path), arrays)
+    assert shapes["draws"] == [4, 100, 500] and not (tmp_path / "draws_index.npy").exists()
+    assert np.array_equal(np.load(tmp_path / "draws.npy"), arrays["draws"])
+    ns = np.load(tmp_path / "num_steps.npy")
+    assert ns.dtype == np.float64 and np.array_equal(ns, arrays["num_steps"])
+    assert np.load(tmp_path / "diverging.npy").dtype == np.float64 and np.load(tmp_path / "step_size.npy").dtype == np.float64
+    # over the cap: a fixed, seeded sample of the last axis, its indices beside it, the same on every call
+    limit = 200_000
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), arrays, limit=limit)
+        files = list((tmp_path / sub).iterdir())
+        assert sum(f.stat().st_size for f in files) <= limit + 128 * len(files)
+    idx = np.load(tmp_path / "a" / "draws_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and 0 < idx.size < 500
+    got = np.load(tmp_path / "a" / "draws.npy")
+    assert np.array_equal(got, arrays["draws"][..., idx.astype(np.int64)])
+    assert np.array_equal(got, np.load(tmp_path / "b" / "draws.npy"))

@@ -1,6 +1,6 @@
 set -u
 OUT=gpurun_out/f; mkdir -p $OUT; ROOT=$(pwd)
-python bench.py --workload occu_re --no-e2e --full-line > $OUT/bench_re.json 2> $OUT/bench_re.err; echo rc=$?
+python bench.py --full --workload occu_re --no-e2e --full-line > $OUT/bench_re.json 2> $OUT/bench_re.err; echo rc=$?
 python tools/time_re.py > $OUT/time_re.txt 2>&1
 python tools/time_models.py > $OUT/time_models.txt 2>&1
 python tools/stamps_re.py > $OUT/stamps_re.txt 2>&1
