@@ -35,6 +35,11 @@ class bl_beta_prior(C.Structure):
     _fields_ = [("a", C.c_double), ("b", C.c_double)]
 
 
+class bl_comb_dims(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in
+                ("n_sites", "n_periods", "n_pc", "n_aru", "n_scores", "n_site_covs", "n_pc_covs", "n_aru_covs")]
+
+
 FP_CONSTANT, FP_UNOCCUPIED = 1, 2
 
 
@@ -65,7 +70,7 @@ EXPORTS = (
     "bl_abi_version", "bl_last_error", "bl_device_count", "bl_dataset_create", "bl_dataset_create_rn", "bl_dataset_create_dyn", "bl_dataset_destroy",
     "bl_dataset_param_dim", "bl_logp_grad", "bl_nuts_run", "bl_nuts_launch", "bl_nuts_poll",
     "bl_nuts_abort", "bl_nuts_wait", "bl_nuts_fetch", "bl_nuts_elapsed_ms", "bl_nuts_device_draws",
-    "bl_nuts_geometry", "bl_nuts_lane_group", "bl_nuts_kernel_name", "bl_nuts_debug_counters", "bl_deterministic", "bl_predict", "bl_predict_counts", "bl_predict_scores", "bl_dataset_create_fp", "bl_dataset_create_cop", "bl_dataset_create_nmix", "bl_dataset_create_re", "bl_dataset_create_re_fp", "bl_dataset_create_nmix_re", "bl_dataset_create_rn_re", "bl_dataset_create_rn_fp", "bl_dataset_create_cop_re", "bl_dataset_create_cs", "bl_dataset_set_prior_family", "bl_rng_streams", "bl_adaptation_schedule",
+    "bl_nuts_geometry", "bl_nuts_lane_group", "bl_nuts_kernel_name", "bl_nuts_debug_counters", "bl_deterministic", "bl_predict", "bl_predict_counts", "bl_predict_scores", "bl_dataset_create_fp", "bl_dataset_create_cop", "bl_dataset_create_nmix", "bl_dataset_create_re", "bl_dataset_create_re_fp", "bl_dataset_create_nmix_re", "bl_dataset_create_rn_re", "bl_dataset_create_rn_fp", "bl_dataset_create_cop_re", "bl_dataset_create_cs", "bl_dataset_create_comb", "bl_dataset_set_prior_family", "bl_rng_streams", "bl_adaptation_schedule",
     "bl_comm_rccl_version", "bl_comm_unique_id", "bl_comm_init_rank", "bl_comm_init_all", "bl_comm_info", "bl_comm_destroy",
     "bl_gather_draws", "bl_result_block_layout", "bl_gather_unpack", "bl_host_alloc", "bl_host_free",
     "bl_nuts_env_overrides", "bl_env_overrides",
@@ -118,6 +123,9 @@ def load():
                                                C.POINTER(bl_normal_prior), C.POINTER(bl_normal_prior), C.c_int, C.POINTER(vp)]
         L.bl_dataset_create_cs.argtypes = [C.POINTER(bl_dims), fp, fp, fp, dp, dp, C.POINTER(bl_normal_prior),
                                            C.POINTER(bl_normal_prior), C.c_int, C.POINTER(vp)]
+        L.bl_dataset_create_comb.argtypes = [C.POINTER(bl_comb_dims), fp, fp, fp, fp, fp, fp, C.POINTER(bl_beta_prior),
+                                             C.POINTER(bl_beta_prior), dp, dp, C.POINTER(bl_normal_prior), C.POINTER(bl_normal_prior),
+                                             C.c_int, C.POINTER(vp)]
         L.bl_dataset_set_prior_family.argtypes = [vp, C.c_int, C.c_int]
         L.bl_dataset_destroy.argtypes = [vp]
         L.bl_dataset_param_dim.argtypes = [vp, ip]

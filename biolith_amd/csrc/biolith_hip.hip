@@ -179,6 +179,7 @@ struct bl_dataset {
     int device = 0;
     int model = 0;          // 0 occu, 1 occu_rn, 2 occu with false positives, 3 occu_cop, 4 nmixture, 6 occu with random effects
     BlReModel re{};         // model 6 (re_kernel.hpp); D is then the full coordinate count
+    BlCombModel comb{};     // model 6 kind 8 (occu_comb): its blocks' shapes and rate priors
     float *d_restate = nullptr; // model 6: sampler state [C][k][RE_SLOTS][dl_max]
     size_t restate_bytes = 0;
     float *d_tab = nullptr; // nmixture: B[t][n][site] = sum_j m log C(n, y_j), -inf below the largest count
@@ -216,7 +217,7 @@ struct bl_dataset {
     long long *d_nleap = nullptr, *d_dbg = nullptr;
     int *d_loc = nullptr;
     uint32_t *d_rng = nullptr;
-    float *d_scores = nullptr; // occu_cs: scores, site-fastest [T J][n_stride]
+    float *d_scores = nullptr; // occu_cs: scores, site-fastest [T J][n_stride]; occu_comb: its own rows (re_kernel.hpp: bl_comb_site_pass)
     unsigned long long *d_xchg = nullptr;
     size_t xchg_bytes = 0;
     int *h_abort = nullptr, *d_abort = nullptr;
@@ -388,7 +389,9 @@ extern "C" int bl_predict(bl_dataset *ds, int n_draws, const float *draws, uint6
         return bl_fail(BL_ERR_UNSUPPORTED, "bl_predict: the count models (occu_cop, nmixture) use bl_predict_counts");
     if (ds->model == 6 && ds->re.kind == 1)
         return bl_fail(BL_ERR_UNSUPPORTED, "bl_predict: not built for occu_cs (its observed site is a continuous score)");
-    if (ds->model == 6 && (ds->re.kind == 3 || ds->re.kind >= 6))
+    if (ds->model == 6 && ds->re.kind == 8)
+        return bl_fail(BL_ERR_UNSUPPORTED, "bl_predict: not built for occu_comb");
+    if (ds->model == 6 && (ds->re.kind == 3 || ds->re.kind == 6 || ds->re.kind == 7))
         return bl_fail(BL_ERR_UNSUPPORTED, "bl_predict: the count models' sampled sites are counts (bl_predict_counts)");
     if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
     int rc = set_device(ds);
@@ -592,7 +595,7 @@ extern "C" int bl_predict_counts(bl_dataset *ds, int n_draws, const float *draws
 {
     if (!ds || !draws || n_draws <= 0 || (!latent && !y)) return bl_fail(BL_ERR_INVALID, "bl_predict_counts: bad argument");
     const bool nmix_re = ds->model == 6 && ds->re.kind == 3; // the N-mixture model with random effects
-    const bool cop_re = ds->model == 6 && ds->re.kind >= 6;  // occu_cop with random effects (and a false-positive rate: kind 7)
+    const bool cop_re = ds->model == 6 && (ds->re.kind == 6 || ds->re.kind == 7); // occu_cop with random effects (and a false-positive rate: kind 7)
     if (ds->model != 3 && ds->model != 4 && !nmix_re && !cop_re)
         return bl_fail(BL_ERR_UNSUPPORTED, "bl_predict_counts: for the count models (occu_cop, nmixture); use bl_predict");
     if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
@@ -1247,6 +1250,7 @@ static hipError_t re_nuts_dispatch_lds(const BlReRun &run, int grid, size_t lds,
 }
 static hipError_t re_nuts_dispatch(int mk, const BlReRun &run, int grid, size_t lds, hipStream_t st)
 {
+    if (run.m.kind == 8) return mk == 4 ? re_nuts_dispatch_lds<4, 8>(run, grid, lds, st) : re_nuts_dispatch_lds<16, 8>(run, grid, lds, st);
     if (run.m.kind == 2) return mk == 4 ? re_nuts_dispatch_lds<4, 2>(run, grid, lds, st) : re_nuts_dispatch_lds<16, 2>(run, grid, lds, st);
     if (run.m.kind == 3) return mk == 4 ? re_nuts_dispatch_lds<4, 3>(run, grid, lds, st) : re_nuts_dispatch_lds<16, 3>(run, grid, lds, st);
     if (run.m.kind == 4) return mk == 4 ? re_nuts_dispatch_lds<4, 4>(run, grid, lds, st) : re_nuts_dispatch_lds<16, 4>(run, grid, lds, st);
@@ -1500,6 +1504,116 @@ extern "C" int bl_dataset_create_cs(const bl_dims *dims, const float *site_covs,
     return BL_OK;
 }
 
+// occu_comb (biolith/models/occu_comb.py:150-349): point counts, ARU detections and scores on the random-effects kernels' framework
+// (kind 8), one species, no effects: D = G = (Ks + 1) + (Kpc + 1) + (Karu + 1) + 6.  The handle is made as a plain occu handle
+// over the point counts (device, events, the abort flag); the kind-8 rows replace what the kernels read.
+extern "C" int bl_dataset_create_comb(const bl_comb_dims *cd, const float *site_covs, const float *pc_covs, const float *pc_obs,
+                                      const float *aru_covs, const float *aru_obs, const float *scores, const bl_beta_prior *prior_fc,
+                                      const bl_beta_prior *prior_fu, const double *prior_mu, const double *prior_sigma,
+                                      const bl_normal_prior *prior_beta, const bl_normal_prior *prior_alpha, int device, bl_dataset **out)
+{
+    if (!cd || !pc_obs || !aru_obs || !scores || !prior_mu || !prior_sigma || !out) return bl_fail(BL_ERR_INVALID, "NULL argument");
+    const int N = cd->n_sites, T = cd->n_periods, Jp = cd->n_pc, Ja = cd->n_aru, Js = cd->n_scores;
+    const int Ks = cd->n_site_covs, Kp = cd->n_pc_covs, Ka = cd->n_aru_covs;
+    if (N <= 0 || T <= 0 || Jp < 0 || Ja < 0 || Js < 0 || Ks < 0 || Kp < 0 || Ka < 0) return bl_fail(BL_ERR_INVALID, "negative dimension");
+    if (Ks > BL_RE_MAXK || Kp > BL_RE_MAXK || Ka > BL_RE_MAXK)
+        return bl_fail(BL_ERR_UNSUPPORTED, "occu_comb kernels are built for at most %d covariates per block (Ks=%d, Kpc=%d, Karu=%d)",
+                       BL_RE_MAXK, Ks, Kp, Ka);
+    if ((Kp > 0 && !pc_covs) || (Ka > 0 && !aru_covs) || (Ks > 0 && !site_covs)) return bl_fail(BL_ERR_INVALID, "NULL covariates");
+    const double fca = prior_fc ? prior_fc->a : 2.0, fcb = prior_fc ? prior_fc->b : 5.0, fua = prior_fu ? prior_fu->a : 2.0, fub = prior_fu ? prior_fu->b : 5.0;
+    if (!(fca > 0.0) || !(fcb > 0.0) || !(fua > 0.0) || !(fub > 0.0) || !std::isfinite(fca + fcb + fua + fub))
+        return bl_fail(BL_ERR_INVALID, "Beta prior needs finite a, b > 0");
+    if (!(prior_mu[1] > 0.0) || !(prior_mu[3] > 0.0) || !(prior_sigma[0] > 0.0) || !(prior_sigma[1] > 0.0) || !(prior_sigma[2] > 0.0) || !(prior_sigma[3] > 0.0))
+        return bl_fail(BL_ERR_INVALID, "occu_comb priors need positive scales / concentrations / rates");
+    // the handle: a plain occu handle over the point counts (at least one replicate: a stand-in of NaN when there are none)
+    bl_dims pd{1, N, T, Jp > 0 ? Jp : 1, Ks, Kp};
+    std::vector<float> nan_obs;
+    const float *pobs = pc_obs, *pcov = pc_covs;
+    if (Jp == 0) { nan_obs.assign((size_t)N * T, NAN); pobs = nan_obs.data(); pd.n_obs_covs = 0; pcov = nullptr; }
+    int rc = dataset_create_impl(ModelOpts{}, &pd, site_covs, pcov, pobs, prior_beta, prior_alpha, device, out);
+    if (rc) return rc;
+    bl_dataset *ds = *out;
+    // ---- rows: site covariates (+ a zero row), PC visits, ARU visits, six rows per period (bl_comb_site_pass) ----
+    const int ns = ds->n_stride, vp = Kp + 1, va = Ka + 1, KSc = Ks + 1;
+    const int r_pc = KSc, r_ar = r_pc + T * Jp * vp, r_per = r_ar + T * Ja * va, n_rows = r_per + 6 * T;
+    std::vector<float> rows((size_t)n_rows * ns, 0.0f);
+    const double LOG_TINY = -87.33654475055310898657;
+    for (int i = 0; i < N; i++) {
+        bool site_nan = false;
+        for (int k = 0; k < Ks; k++) {
+            float x = site_covs[(size_t)i * Ks + k];
+            if (std::isnan(x)) { site_nan = true; x = 0.0f; }
+            rows[(size_t)k * ns + i] = x;
+        }
+        for (int t = 0; t < T; t++) {
+            // one block of sign-folded visits: returns (detections, non-detections)
+            auto block = [&](int J, int K, int vw, int r0, const float *covs, const float *obs, int &nd, int &nn) {
+                nd = nn = 0;
+                for (int j = 0; j < J; j++) {
+                    const size_t o = ((size_t)i * T + t) * J + j;
+                    bool nan = site_nan;
+                    for (int k = 0; k < K; k++) nan = nan || std::isnan(covs[o * K + k]);
+                    const float y = obs[o];
+                    const float c = (nan || !std::isfinite(y)) ? 0.0f : (y != 0.0f ? 1.0f : -1.0f);
+                    nd += c > 0.0f; nn += c < 0.0f;
+                    const size_t rr = (size_t)r0 + (size_t)(t * J + j) * vw;
+                    rows[rr * ns + i] = c;
+                    for (int k = 0; k < K; k++) rows[(rr + 1 + k) * ns + i] = c == 0.0f ? 0.0f : c * covs[o * K + k];
+                }
+            };
+            int pd_, pn_, ad_, an_;
+            block(Jp, Kp, vp, r_pc, pc_covs, pc_obs, pd_, pn_);
+            block(Ja, Ka, va, r_ar, aru_covs, aru_obs, ad_, an_);
+            // the period's scores: count, mean, sum of squared deviations (f64 on the host)
+            double n = 0.0, mean = 0.0, m2 = 0.0;
+            for (int j = 0; j < Js && !site_nan; j++) {
+                const double x = scores[((size_t)i * T + t) * Js + j];
+                if (!std::isfinite(x)) continue;
+                n += 1.0;
+                const double dlt = x - mean;
+                mean += dlt / n;
+                m2 += dlt * (x - mean);
+            }
+            const size_t rp = (size_t)r_per + 6 * t;
+            rows[rp * ns + i] = (float)(pd_ * LOG_TINY);
+            rows[(rp + 1) * ns + i] = (float)ad_; rows[(rp + 2) * ns + i] = (float)an_;
+            rows[(rp + 3) * ns + i] = (float)n; rows[(rp + 4) * ns + i] = (float)mean; rows[(rp + 5) * ns + i] = (float)m2;
+        }
+    }
+    if (hipMalloc((void **)&ds->d_scores, rows.size() * 4) != hipSuccess ||
+        hipMemcpy(ds->d_scores, rows.data(), rows.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        bl_dataset_destroy(ds); *out = nullptr;
+        return bl_fail(BL_ERR_NO_DEVICE, "occu_comb: row upload failed");
+    }
+    const bl_normal_prior pb = prior_beta ? *prior_beta : bl_normal_prior{0.0, 1.0}, pa = prior_alpha ? *prior_alpha : bl_normal_prior{0.0, 1.0};
+    BlReModel &m = ds->re;
+    m.rows = ds->d_scores; m.n_sites = N; m.n_stride = ns; m.T = T; m.J = std::max(std::max(Jp, Ja), 1);
+    m.Ks = Ks; m.Ko = std::max(Kp, Ka); m.KS = KSc; m.KO = m.Ko;
+    BlCombModel &cm = ds->comb;
+    cm.Jpc = Jp; cm.Jaru = Ja; cm.Jsc = Js; cm.Kpc = Kp; cm.Karu = Ka; cm.r_aru = r_ar - r_pc; cm.r_per = r_per - r_pc;
+    cm.fc_a = (float)fca; cm.fc_b = (float)fcb; cm.fu_a = (float)fua; cm.fu_b = (float)fub;
+    m.site_re = 0; m.obs_re = 0; m.kind = 8; m.scores = nullptr;
+    m.G0 = Ks + Kp + Ka + 3; m.G = m.G0 + 6; m.D = m.G;
+    m.n_species = 1; m.G0s = m.G0; m.sp = 0; m.cb = 0; m.rv0 = KSc; m.sp_rows = n_rows - KSc;
+    m.o_fp = -1; m.o_phi_s = m.o_phi_o = m.o_u = m.o_v = m.o_e = -1;
+    m.loc_b = (float)pb.loc; m.isc2_b = (float)(1.0 / (pb.scale * pb.scale)); m.loc_a = (float)pa.loc; m.isc2_a = (float)(1.0 / (pa.scale * pa.scale));
+    m.l1_b = 0.0f; m.l1_a = 0.0f; m.hn_is2_s = m.hn_is2_o = 0.0f;
+    for (int k = 0; k < 4; k++) { m.cs_mu[k] = (float)prior_mu[k]; m.cs_sg[k] = (float)prior_sigma[k]; }
+    // constants of the potential: the coefficients' Normal normalisers, the rates' log B(a, b), those of mu0 / mu1 and the Gammas'
+    const double HL2PI = 0.91893853320467274178;
+    m.u_const = (Ks + 1) * (std::log(pb.scale) + HL2PI) + (Kp + Ka + 2) * (std::log(pa.scale) + HL2PI);
+    m.u_const += std::lgamma(fca) + std::lgamma(fcb) - std::lgamma(fca + fcb) + std::lgamma(fua) + std::lgamma(fub) - std::lgamma(fua + fub);
+    m.u_const += std::log(prior_mu[1]) + std::log(prior_mu[3]) + 2.0 * HL2PI;
+    for (int f = 0; f < 2; f++) m.u_const += -prior_sigma[2 * f] * std::log(prior_sigma[2 * f + 1]) + std::lgamma(prior_sigma[2 * f]);
+    m.n_total = N; m.s0 = 0; m.x_u = m.x_v = m.x_e = -1;
+    m.n_rows = n_rows;
+    re_geometry(m, N, 0, 0);
+    // (bl_dataset_set_prior_family counts the alpha coefficients as Ko + 1: both detection blocks)
+    ds->Ko = Kp + Ka + 1;
+    ds->model = 6; ds->D = m.D;
+    return BL_OK;
+}
+
 static int re_logp_grad(bl_dataset *ds, int B, const double *theta, double *U, double *grad)
 {
     const size_t D = ds->D;
@@ -1515,6 +1629,13 @@ static int re_logp_grad(bl_dataset *ds, int B, const double *theta, double *U, d
     BL_HIP(hipMemcpy(d_th, th32.data(), th32.size() * 4, hipMemcpyHostToDevice));
     BlReModel m = ds->re;
     const size_t lds = re_geometry(m, m.n_sites, 0, 0);
+    if (m.kind == 8) { // occu_comb: its own parity kernel (m.Ko = the wider detection block)
+        const bool c4 = m.Ks <= 4 && m.Ko <= 4;
+        const void *f = c4 ? (const void *)bl_comb_logp_kernel<4> : (const void *)bl_comb_logp_kernel<16>;
+        if (lds) BL_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (c4) hipLaunchKernelGGL(bl_comb_logp_kernel<4>, dim3(B), dim3(BL_RE_NT), lds, nullptr, m, ds->comb, B, d_th, d_work, d_U, d_grad);
+        else hipLaunchKernelGGL(bl_comb_logp_kernel<16>, dim3(B), dim3(BL_RE_NT), lds, nullptr, m, ds->comb, B, d_th, d_work, d_U, d_grad);
+    } else
     // capacity 4 (the common case: short register arrays) or 16 covariates per side
     if (m.Ks <= 4 && m.Ko <= 4) {
         if (lds) BL_HIP(hipFuncSetAttribute((const void *)bl_re_logp_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1689,6 +1810,7 @@ static int re_nuts_launch(bl_dataset *ds, const bl_nuts_config *cfg, hipStream_t
     }
     BlReRun run{};
     run.m = g;
+    run.comb = ds->comb;
     const size_t lds = re_geometry(run.m, nloc, 1, dl_max);
     const bool cap4 = g.Ks <= 4 && g.Ko <= 4;
     run.num_chains = C; run.num_warmup = W; run.num_samples = S; run.max_depth = max_depth;
@@ -2077,6 +2199,8 @@ extern "C" int bl_deterministic(bl_dataset *ds, int n_draws, const float *draws,
     if (!ds || !draws || n_draws <= 0) return bl_fail(BL_ERR_INVALID, "bl_deterministic: bad argument");
     if (ds->nsp > 1) return bl_fail(BL_ERR_UNSUPPORTED, "bl_deterministic: a joint-species handle samples; take the sites from one handle per species");
     if (ds->model == 8) return bl_fail(BL_ERR_UNSUPPORTED, "bl_deterministic: the dynamic occupancy model's sites (psi, gamma, eps) are formed by the caller from the draws");
+    if (ds->model == 6 && ds->re.kind == 8)
+        return bl_fail(BL_ERR_UNSUPPORTED, "bl_deterministic: occu_comb's sites (psi, PC / ARU detection probabilities) are formed by the caller from the draws");
     if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
     int rc = set_device(ds);
     if (rc) return rc;
@@ -2107,7 +2231,7 @@ extern "C" int bl_deterministic(bl_dataset *ds, int n_draws, const float *draws,
         }
         if (prob_detection) {
             hipLaunchKernelGGL(bl_pdet_kernel, grid, block, 0, nullptr, ds->d_wraw, ds->n_stride, N, T, J, ds->Ks, ds->Ko, D, d_draws, n0, n1, d_out,
-                               ds->model == 6 && ds->re.kind >= 6 ? 3 : ds->model /* occu_cop with effects: rate_detection = exp(nu) */,
+                               ds->model == 6 && (ds->re.kind == 6 || ds->re.kind == 7) ? 3 : ds->model /* occu_cop with effects: rate_detection = exp(nu) */,
                                ds->model == 6 ? ds->re.o_v : -1, ds->model == 6 ? ds->re.o_e : -1);
             BL_HIP(hipGetLastError());
             BL_HIP(hipMemcpy(prob_detection + (size_t)n0 * J * T * N, d_out, (size_t)(n1 - n0) * J * T * N * 4, hipMemcpyDeviceToHost));

@@ -26,7 +26,12 @@
 #define BL_RE_OX(MK) (2 * (MK) + 3)
 #define BL_RE_NV1(MK) (2 * (MK) + 11)
 #define BL_RE_NRED_OF(MK) (BL_RE_NV1(MK) > 26 ? BL_RE_NV1(MK) : 26) // widest block reduction (the second one: 3 + 2 x 10 checkpoints)
-#define BL_RE_NRED_MAX BL_RE_NRED_OF(BL_RE_MAXK)
+// per KIND: occu_comb (kind 8) has a second alpha block, so its first reduction is wider -- OX = 3MK+4, then dmu0, dmu1, prior
+// quadratic, abort, XCC census (2), dlog sigma0, dlog sigma1, dphi_c, dphi_u.  Every other kind keeps the sizes above.
+#define BL_RE_OX_K(MK, KIND) ((KIND) == 8 ? 3 * (MK) + 4 : BL_RE_OX(MK))
+#define BL_RE_NV1_K(MK, KIND) ((KIND) == 8 ? 3 * (MK) + 14 : BL_RE_NV1(MK))
+#define BL_RE_NRED_K(MK, KIND) (BL_RE_NV1_K(MK, KIND) > 26 ? BL_RE_NV1_K(MK, KIND) : 26)
+#define BL_RE_NRED_MAX BL_RE_NRED_K(BL_RE_MAXK, 8) // (sizes the exchange buffer of every kind)
 #define BL_RE_SMAX 8             // species under one chain (each needs at least one of the chain's <= 32 workgroups)
 #define BL_RE_VB 4               // visits whose loads are issued together in the site pass
 
@@ -66,6 +71,14 @@ struct BlReModel {
     // (visit = (m y, m, w..)) and its data-only table tab[t][n][site] = sum_j m log C(n, y_j) (-inf below the largest count)
     const float *tab;
     int tab_ld, max_abundance;
+};
+
+// kind 8 (occu_comb) only, in a struct of its own so that BlReModel -- and with it every other kind's code -- is unchanged: replicates
+// and covariates of the point-count and ARU blocks, replicates of the scores; the ARU visit rows and the per-period rows start
+// r_aru / r_per rows after the first visit row; Beta priors of the two rates
+struct BlCombModel {
+    int Jpc, Jaru, Jsc, Kpc, Karu, r_aru, r_per;
+    float fc_a, fc_b, fu_a, fu_b;
 };
 
 // The dataset's rows for this workgroup: staged into dynamic LDS once when they fit, else read from device memory (L2).
@@ -114,6 +127,7 @@ struct BlReRun {
     unsigned char *diverging; int *num_steps; float *accept_prob, *potential, *step_size, *inv_mass;
     long long *nleap; int *status;
     long long *dbg;             // [32] section cycle counters (BL_STAMPS diagnostic builds; chain 0, thread 0)
+    BlCombModel comb;           // kind 8 only
 };
 #ifdef BL_STAMPS
 #define BL_RE_T(i) { const long long now_ = (long long)clock64(); st_acc[i] += now_ - st_prev; st_prev = now_; }
@@ -1066,6 +1080,211 @@ __device__ __forceinline__ double bl_cs_extra_potential(const BlReModel &m, cons
     return U; // (constants: m.u_const)
 }
 
+// ---- occu_comb (kind 8; biolith/models/occu_comb.py:150-349): point counts, ARU detections and classifier scores share one z ----
+// Coordinates: [beta | alpha_PC | alpha_ARU | phi_c = logit fc | phi_u = logit fu | mu0 | log(mu1 - mu0) | log sigma0 | log sigma1].
+// Rows (one species): the site covariates, then from rv the point-count visits (c, c w_1 .. c w_Kpc), the ARU visits
+// (c, c w_1 .. c w_Karu) -- c = +1 detection, -1 none, 0 masked -- then six rows per period: n_det_pc log(tiny), ARU detections,
+// ARU non-detections, and the period's unmasked scores as count n, mean m and sum of squared deviations M2.  Per (site, period):
+//   L1 = log psi + sum_PC log sigma(u) + sum_ARU [det: log(q + fc (1 - q)), non: log(1 - q) + log(1 - fc)] + sum_sc log N(s; mu1, sigma1)
+//   L0 = log(1 - psi) + n_det_pc log(tiny) + n_det_aru log p0 + n_non_aru log(1 - p0) + sum_sc log N(s; mu0, sigma0),  p0 = 1 - (1 - fc)(1 - fu)
+// (sum_sc log N(s; mu, sigma) = -n (log sigma + log(2 pi) / 2) - (M2 + n (m - mu)^2) / (2 sigma^2): no per-score work), and with
+// r = sigma(L1 - L0): d/d eta = r - psi, d/d alpha_PC and alpha_ARU = r dL1, d/d fc = r dL1 + (1 - r) dL0, d/d fu = (1 - r) dL0, the
+// (mu1, sigma1) moments weighted by r, (mu0, sigma0) by 1 - r.  part: [0] ll, [1 .. MK+1] beta, [MK+2 .. 2MK+2] alpha_PC,
+// [2MK+3 .. 3MK+3] alpha_ARU, [OX] mu0, [OX+1] mu1, [OX+6] log sigma0, [OX+7] log sigma1, [OX+8] phi_c, [OX+9] phi_u (OX = 3MK+4);
+// [OX+2 .. OX+5] are left 0 for the caller.
+template <int MK>
+__device__ __forceinline__ void bl_comb_site_pass(const BlReModel &m, const BlCombModel &cm, const float *__restrict__ rows, int ns, int rv,
+                                                  const float *__restrict__ z, float (&part)[3 * MK + 14])
+{
+    constexpr int OX = 3 * MK + 4;
+    const BlReSiteMap sm = bl_re_site_map(m);
+    const int tps = sm.tps, S = sm.S, sub = sm.sub;
+    const int T = m.T, Ks = m.Ks, Kpc = cm.Kpc, Kar = cm.Karu, Jpc = cm.Jpc, Jar = cm.Jaru, vp = Kpc + 1, va = Kar + 1;
+    const int r_ar = rv + cm.r_aru, r_pr = rv + cm.r_per;
+    // (the detection coefficients are read where a visit uses them, not kept: two more arrays of MK + 1 live across the pass pushed
+    // the capacity-4 sampler into scratch memory)
+    float beta[MK + 1];
+#pragma unroll
+    for (int k = 0; k <= MK; k++) {
+        const float b = z[min(k, Ks)];
+        beta[k] = k <= Ks ? b : 0.0f;
+    }
+    const float *apc = z + Ks + 1, *aar = z + Ks + Kpc + 2;
+    const float TINY = 1.1754944e-38f, LOG_EPS = -15.9423847f, HL2PI = 0.9189385f;
+    // the rates and their complements, f = sigmoid(phi), 1 - f = sigmoid(-phi)
+    auto rate = [&](float phi, float &f, float &g) {
+        const float e = bl_exp(-fabsf(phi)), r = bl_rcp(1.0f + e);
+        f = (phi > 0.0f ? 1.0f : e) * r; g = (phi > 0.0f ? e : 1.0f) * r;
+    };
+    float fc, gc, lp0, lq0;
+    {
+        float fu, gu;
+        rate(z[m.G0], fc, gc);
+        rate(z[m.G0 + 1], fu, gu);
+        // the z = 0 ARU probability, clamped to [tiny, 1 - eps] as numpyro clamps it (a clamped side has no gradient)
+        lp0 = bl_log(fmaxf(fmaf(fu, gc, fc), TINY));
+        lq0 = fmaxf(bl_log(gc) + bl_log(gu), LOG_EPS);
+    }
+    const float lgc = bl_log(gc), ngc = -bl_rcp(gc);
+    const float mu0 = z[m.G0 + 2], mu1 = mu0 + bl_exp(z[m.G0 + 3]);
+    const float c0 = z[m.G0 + 4] + HL2PI, c1 = z[m.G0 + 5] + HL2PI;       // log sigma + log(2 pi) / 2
+    const float is0 = bl_exp(-2.0f * z[m.G0 + 4]), is1 = bl_exp(-2.0f * z[m.G0 + 5]); // 1 / sigma^2
+    // d / d fc of the z = 1 ARU terms, and the z = 0 branch's weight on its ARU detections / non-detections (their gradients at the end)
+    float gfc = 0.0f, w0d = 0.0f, w0n = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3 * MK + 14; k++) part[k] = 0.0f;
+    for (int rd = 0; rd < sm.rounds; rd++) {
+        const int i_raw = rd * sm.ngrp + sm.grp;
+        const bool live = i_raw < sm.cnt;
+        const int i = sm.first + (live ? i_raw : sm.cnt - 1); // idle groups shadow the class's last site (their results are dropped)
+        float eta = beta[0];
+#pragma unroll
+        for (int k = 0; k < MK; k++) {
+            const float xk = rows[min(k, Ks) * ns + i]; // (k == Ks: a zero row, discarded)
+            eta = fmaf(k < Ks ? xk : 0.0f, beta[k + 1], eta);
+        }
+        const float ee = bl_exp(-fabsf(eta)), lop = bl_log(1.0f + ee);
+        const float log_psi = fminf(eta, 0.0f) - lop, log_1mpsi = fminf(-eta, 0.0f) - lop;
+        const float psi = (eta > 0.0f ? 1.0f : ee) * bl_rcp(1.0f + ee);
+        float dl_deta = 0.0f;
+        for (int t = 0; t < T; t++) {
+            // A visit's row (c, c w_1 .. c w_K) and u = c nu; w[k] = 0 beyond the block's K.
+            auto visit = [&](int r0, int K, const float *al, float (&w)[MK + 1]) {
+#pragma unroll
+                for (int k = 0; k <= MK; k++) {
+                    const float wk = rows[r0 + min(k, K) * ns];
+                    w[k] = k <= K ? wk : 0.0f;
+                }
+                float u = w[0] * al[0];
+#pragma unroll
+                for (int k = 1; k <= MK; k++) u = fmaf(w[k], al[min(k, K)], u);
+                return u;
+            };
+            // pass 1: the z = 1 sums of this thread's visits -- PC, ARU, the ARU sum's d / d fc -- pooled over the site's threads
+            float a_pc = 0.0f, a_ar = 0.0f, d_fc = 0.0f;
+            for (int j = sub; j < Jpc; j += tps) {
+                float w[MK + 1];
+                const float u = visit((rv + (t * Jpc + j) * vp) * ns + i, Kpc, apc, w);
+                a_pc = fmaf(w[0] * w[0], fminf(u, 0.0f) - bl_log(1.0f + bl_exp(-fabsf(u))), a_pc); // log sigma(u), masked visits weigh 0
+            }
+            for (int j = sub; j < Jar; j += tps) {
+                float w[MK + 1];
+                const float u = visit((r_ar + (t * Jar + j) * va) * ns + i, Kar, aar, w);
+                const float e = bl_exp(-fabsf(u)), op = 1.0f + e, rop = bl_rcp(op);
+                const float sp = (u > 0.0f ? 1.0f : e) * rop, sn = (u > 0.0f ? e : 1.0f) * rop; // sigma(u), sigma(-u)
+                const bool det = w[0] > 0.0f, non = w[0] < 0.0f;
+                // detection (u = nu): log(q + fc (1 - q)); non-detection (u = -nu): log(1 - q) + log(1 - fc)
+                const float p1 = fmaf(fc, sn, sp);
+                a_ar += det ? bl_log(p1) : (non ? fminf(u, 0.0f) - bl_log(op) + lgc : 0.0f);
+                d_fc += det ? sn * bl_rcp(p1) : (non ? ngc : 0.0f);
+            }
+            for (int msk = S; msk < 64; msk <<= 1) {
+                a_pc += __shfl_xor(a_pc, msk);
+                a_ar += __shfl_xor(a_ar, msk);
+                d_fc += __shfl_xor(d_fc, msk);
+            }
+            const int rp = (r_pr + 6 * t) * ns + i;
+            const float kb_pc = rows[rp], nd_ar = rows[rp + ns], nn_ar = rows[rp + 2 * ns];
+            const float sc_n = rows[rp + 3 * ns], sc_m = rows[rp + 4 * ns], sc_m2 = rows[rp + 5 * ns];
+            const float d1 = sc_m - mu1, d0 = sc_m - mu0;
+            const float q1 = fmaf(sc_n * d1, d1, sc_m2) * is1, q0 = fmaf(sc_n * d0, d0, sc_m2) * is0; // sum (s - mu)^2 / sigma^2
+            const float A = log_psi + a_pc + a_ar + fmaf(-0.5f, q1, -sc_n * c1);
+            const float B = log_1mpsi + kb_pc + fmaf(nd_ar, lp0, nn_ar * lq0) + fmaf(-0.5f, q0, -sc_n * c0);
+            const float l = bl_logaddexp(A, B);
+            const float q = bl_exp(A - l), qb = 1.0f - q;
+            // pass 2: every thread adds r dL1 / d alpha of its own visits straight into its partial sums (the block sum pools them;
+            // two arrays of MK + 1 carried through pass 1 and shuffled instead pushed the capacity-4 sampler into scratch memory)
+            if (live) {
+                for (int j = sub; j < Jpc; j += tps) {
+                    float w[MK + 1];
+                    const float u = visit((rv + (t * Jpc + j) * vp) * ns + i, Kpc, apc, w);
+                    const float e = bl_exp(-fabsf(u));
+                    const float s = q * (u > 0.0f ? e : 1.0f) * bl_rcp(1.0f + e);   // r sigma(-u)
+#pragma unroll
+                    for (int k = 0; k <= MK; k++) part[MK + 2 + k] = fmaf(s, w[k], part[MK + 2 + k]); // (w carries the sign and the mask)
+                }
+                for (int j = sub; j < Jar; j += tps) {
+                    float w[MK + 1];
+                    const float u = visit((r_ar + (t * Jar + j) * va) * ns + i, Kar, aar, w);
+                    const float e = bl_exp(-fabsf(u)), rop = bl_rcp(1.0f + e);
+                    const float sp = (u > 0.0f ? 1.0f : e) * rop, sn = (u > 0.0f ? e : 1.0f) * rop;
+                    const float du = q * (w[0] > 0.0f ? gc * sp * sn * bl_rcp(fmaf(fc, sn, sp)) : sn);
+#pragma unroll
+                    for (int k = 0; k <= MK; k++) part[2 * MK + 3 + k] = fmaf(du, w[k], part[2 * MK + 3 + k]);
+                }
+            }
+            if (live && sub == 0) {
+                part[0] += l;
+                part[OX] = fmaf(qb, sc_n * d0 * is0, part[OX]);
+                part[OX + 1] = fmaf(q, sc_n * d1 * is1, part[OX + 1]);
+                part[OX + 6] = fmaf(qb, q0 - sc_n, part[OX + 6]);
+                part[OX + 7] = fmaf(q, q1 - sc_n, part[OX + 7]);
+                gfc = fmaf(q, d_fc, gfc);
+                w0d = fmaf(qb, nd_ar, w0d);
+                w0n = fmaf(qb, nn_ar, w0n);
+            }
+            dl_deta += q - psi;
+        }
+        if (live && sub == 0) {
+            part[1] += dl_deta;
+#pragma unroll
+            for (int k = 0; k < MK; k++) { // (the site covariates read again rather than kept across the periods)
+                const float xk = rows[min(k, Ks) * ns + i];
+                part[2 + k] = fmaf(dl_deta, k < Ks ? xk : 0.0f, part[2 + k]);
+            }
+        }
+    }
+    float fu, gu;
+    rate(z[m.G0 + 1], fu, gu);
+    const float p0 = fmaf(fu, gc, fc), lq0_raw = lgc + bl_log(gu);
+    // d log p0 / d (fc, fu) = (1 - fu, 1 - fc) / p0, d log(1 - p0) / d (fc, fu) = -1 / (1 - fc), -1 / (1 - fu) -- 0 where clamped
+    const float dp0 = p0 > TINY ? bl_rcp(p0) : 0.0f;
+    const bool open0 = lq0_raw > LOG_EPS;
+    gfc = fmaf(w0d, gu * dp0, fmaf(w0n, open0 ? ngc : 0.0f, gfc));
+    const float gfu = fmaf(w0d, gc * dp0, w0n * (open0 ? -bl_rcp(gu) : 0.0f));
+    part[OX + 8] = gfc * fc * gc; // (d f / d phi = f (1 - f))
+    part[OX + 9] = gfu * fu * gu;
+}
+
+// occu_comb: potential gradient of coordinate d < G from the reduced sums (layout of bl_comb_site_pass).  The regression
+// coefficients' priors as in bl_re_global_grad, the rates' Beta priors in logit space (Jacobian included), and mu0, mu1, sigma0,
+// sigma1 through occu_cs's bl_cs_extra_grad: its coordinates sit two further on and its sums OX_K - OX further on.
+template <int MK>
+__device__ __forceinline__ float bl_comb_global_grad(const BlReModel &m, const BlCombModel &cm, int d, const float *z, const double *red)
+{
+    constexpr int OX = BL_RE_OX_K(MK, 8);
+    if (d < m.G0) {
+        const int nb = m.Ks + 1, npc = cm.Kpc + 1;
+        const bool is_b = d < nb;
+        const int slot = is_b ? 1 + d : (d < nb + npc ? MK + 2 + (d - nb) : 2 * MK + 3 + (d - nb - npc));
+        const float loc = is_b ? m.loc_b : m.loc_a, isc2 = is_b ? m.isc2_b : m.isc2_a, l1 = is_b ? m.l1_b : m.l1_a;
+        const float dth = z[d] - loc;
+        return (float)(-red[slot]) + fmaf(dth, isc2, dth > 0.0f ? l1 : (dth < 0.0f ? -l1 : 0.0f));
+    }
+    const int e = d - m.G0;
+    if (e < 2) { // phi = logit f, f ~ Beta(a, b), Jacobian included: energy a softplus(-phi) + b softplus(phi)
+        const float zd = z[d], ez = bl_exp(-fabsf(zd)), sig = (zd > 0.0f ? 1.0f : ez) * bl_rcp(1.0f + ez);
+        const float a = e == 0 ? cm.fc_a : cm.fu_a, b = e == 0 ? cm.fc_b : cm.fu_b;
+        return (float)(-red[OX + 8 + e]) + (a + b) * sig - a;
+    }
+    return bl_cs_extra_grad<MK>(m, e - 2, z + 2, red + (OX - BL_RE_OX(MK)));
+}
+
+// occu_comb: the potential from the reduced sums (f64): the likelihood, the coefficients' prior energy, the rates' Beta priors
+// and the score parameters' priors (bl_cs_extra_potential on the coordinates two further on); constants in m.u_const
+template <int MK>
+__device__ __forceinline__ double bl_comb_potential(const BlReModel &m, const BlCombModel &cm, const float *z, const double *red)
+{
+    constexpr int OX = BL_RE_OX_K(MK, 8);
+    double U = -red[0] + 0.5 * red[OX + 2] + m.u_const;
+    for (int f = 0; f < 2; f++) {
+        const double phi = z[m.G0 + f], l = log1p(exp(-fabs(phi)));
+        const double a = f == 0 ? cm.fc_a : cm.fu_a, b = f == 0 ? cm.fc_b : cm.fu_b;
+        U += a * (fmax(-phi, 0.0) + l) + b * (fmax(phi, 0.0) + l);
+    }
+    return U + bl_cs_extra_potential(m, z + 2);
+}
+
 // Potential gradient of a fixed effect / log sd coordinate d < G at position z, from the reduced sums of the site pass
 // (red[0 .. 2MK+2]) and of the effects' squares (red[OX] = sum u^2 + v^2, red[OX+1] = sum e^2).
 template <int MK, bool FP = false>
@@ -1143,6 +1362,33 @@ __device__ __forceinline__ float bl_re_prior_quad(const BlReModel &m, const floa
     return pe;
 }
 
+// ---- parity hook of occu_comb: U and dU/dtheta for B positions, one workgroup each (one species, D = G) ----
+template <int MK>
+__global__ void __launch_bounds__(BL_RE_NT) bl_comb_logp_kernel(const BlReModel m, const BlCombModel cm, int B, const float *__restrict__ theta,
+                                                                float *__restrict__ work /*[B][D]*/, double *__restrict__ U,
+                                                                double *__restrict__ grad)
+{
+    constexpr int NRED = BL_RE_NRED_K(MK, 8), OX = BL_RE_OX_K(MK, 8), NV1 = BL_RE_NV1_K(MK, 8);
+    __shared__ float scr[BL_RE_NW * NRED];
+    __shared__ double red[NRED];
+    const int b = blockIdx.x, tid = threadIdx.x, D = m.D;
+    if (b >= B) return;
+    extern __shared__ float bl_re_lds[];
+    float *z = work + (size_t)b * D;
+    for (int d = tid; d < D; d += BL_RE_NT) z[d] = theta[(size_t)b * D + d];
+    int ns = m.n_stride, rv = m.rv0;
+    const float *rows = m.rows;
+    if (m.lds_rows) { rows = bl_re_rows(m, bl_re_lds, ns); rv = m.KS; }
+    __syncthreads();
+    float v[NV1];
+    bl_comb_site_pass<MK>(m, cm, rows, ns, rv, z, v);
+    v[OX + 2] = bl_re_prior_quad(m, z);
+    v[OX + 3] = 0.0f; v[OX + 4] = 0.0f; v[OX + 5] = 0.0f;
+    bl_re_block_sum<NV1, NRED>(v, scr, red);
+    for (int d = tid; d < D; d += BL_RE_NT) grad[(size_t)b * D + d] = (double)bl_comb_global_grad<MK>(m, cm, d, z, red);
+    if (tid == 0) U[b] = bl_comb_potential<MK>(m, cm, z, red);
+}
+
 // ---- parity hook: U and dU/dtheta for B positions (external order in, external order out), one workgroup each ----
 // Several species: the workgroup takes them one after the other (a species' slice = all sites, its own local vectors in `work`).
 template <int MK>
@@ -1217,10 +1463,12 @@ __global__ void __launch_bounds__(BL_RE_NT) bl_re_logp_kernel(const BlReModel gm
 template <int MK, int KIND, bool LROWS, int LT, int EFF = 0>
 __global__ void __launch_bounds__(BL_RE_NT) bl_re_nuts_kernel(const BlReRun R)
 {
-    constexpr int NRED = BL_RE_NRED_OF(MK), OX = BL_RE_OX(MK), NV1 = BL_RE_NV1(MK);
+    constexpr int NRED = BL_RE_NRED_K(MK, KIND), OX = BL_RE_OX_K(MK, KIND), NV1 = BL_RE_NV1_K(MK, KIND);
+    // (occu_comb: one species, so no per-species sums and no staging of the general collect)
+    constexpr int NSP = KIND == 8 ? 1 : BL_RE_SMAX, NX2 = KIND == 8 ? 1 : 32;
     __shared__ float scr[BL_RE_NW * NRED];
-    __shared__ double red[NRED], red2[NRED], red_sp[BL_RE_SMAX * NRED];
-    __shared__ float scr2[32 * NRED];
+    __shared__ double red[NRED], red2[NRED], red_sp[NSP * NRED];
+    __shared__ float scr2[NX2 * NRED];
     __shared__ int xflag;
     // XCD-aware mapping (speed only, as in nuts_kernel.hpp): blocks b and b + 8 share an XCD under the observed round-robin
     // dealing, so chain c takes blocks with b % 8 == c % 8 and its k workgroups share one L2; the first exchange checks it
@@ -1296,7 +1544,9 @@ __global__ void __launch_bounds__(BL_RE_NT) bl_re_nuts_kernel(const BlReRun R)
         const float *z = H(RE_CZ);
         float *g = H(RE_CG);
         BL_RE_T(7)
-        if constexpr (KIND == 1) { // occu_cs: no effects; four more gradient sums
+        if constexpr (KIND == 8) { // occu_comb: no effects; the sums in their final slots
+            bl_comb_site_pass<MK>(m, R.comb, rows, rows_ns, rows_rv, z, v);
+        } else if constexpr (KIND == 1) { // occu_cs: no effects; four more gradient sums
             float part[2 * MK + 7];
             bl_cs_site_pass<MK>(m, rows, rows_ns, z, part);
 #pragma unroll
@@ -1324,7 +1574,7 @@ __global__ void __launch_bounds__(BL_RE_NT) bl_re_nuts_kernel(const BlReRun R)
         v[OX + 4] = tid == 0 ? xcc : 0.0f; v[OX + 5] = tid == 0 ? xcc * xcc : 0.0f;
         BL_RE_T(0)
         ev_first = xc.epoch == 0u;
-        ev_nv = KIND == 1 ? NV1 : ((KIND == 2 || KIND == 5 || KIND == 7) ? OX + 7 : (ev_first ? OX + 6 : OX + 4));
+        ev_nv = (KIND == 1 || KIND == 8) ? NV1 : ((KIND == 2 || KIND == 5 || KIND == 7) ? OX + 7 : (ev_first ? OX + 6 : OX + 4));
         bl_re_block_sum<NV1, NRED>(v, scr, red, ev_nv, xc.k == 1);
         BL_RE_T(9)
         bl_re_publish<NRED>(xc, red, ev_nv);
@@ -1333,11 +1583,19 @@ __global__ void __launch_bounds__(BL_RE_NT) bl_re_nuts_kernel(const BlReRun R)
         const float *z = H(RE_CZ);
         float *g = H(RE_CG);
         // (several species: per-species sums by one poll per species up to three species, else the general form)
-        if (!(m.n_species <= 3 ? bl_re_collect_wave<NRED>(xc, red, &xflag, ev_nv, m.n_species > 1 ? red_sp : nullptr)
-                               : bl_re_collect<NRED>(xc, red, scr2, &xflag, ev_nv, red_sp))) flag = 4;
+        if constexpr (KIND == 8) {
+            if (!bl_re_collect_wave<NRED>(xc, red, &xflag, ev_nv)) flag = 4;
+        } else if (!(m.n_species <= 3 ? bl_re_collect_wave<NRED>(xc, red, &xflag, ev_nv, m.n_species > 1 ? red_sp : nullptr)
+                                      : bl_re_collect<NRED>(xc, red, scr2, &xflag, ev_nv, red_sp))) flag = 4;
         BL_RE_T(10)
         if (ev_first && R.allow_local) xc.local = ((double)R.k * red[OX + 5] == red[OX + 4] * red[OX + 4]); // exact: small integers
         if (red[OX + 3] > 0.0) flag = 5;
+        if constexpr (KIND == 8) {
+            for (int d = tid; d < G; d += BL_RE_NT) g[d] = bl_comb_global_grad<MK>(m, R.comb, d, z, red);
+            const double U = bl_comb_potential<MK>(m, R.comb, z, red);
+            BL_RE_T(1)
+            return U;
+        }
         for (int d = tid; d < G; d += BL_RE_NT)
             g[d] = (KIND == 1 && d >= m.G0) ? bl_cs_extra_grad<MK>(m, d - m.G0, z, red) : bl_re_global_grad<MK, KIND == 2 || KIND == 5 || KIND == 7>(m, d, z[d], red, red_sp, NRED);
         double U = bl_re_potential<KIND == 2 || KIND == 5 || KIND == 7>(m, z, red, red[OX + 2], OX);

@@ -119,9 +119,10 @@ class OccuDataset:
                  model: str = "occu", max_abundance: int = 100, fp_mode: Optional[str] = "constant", prior_fp=(2.0, 5.0),
                  session_duration=None, prior_fp_rate: float = 1.0, site_random_effects: bool = False,
                  obs_random_effects: bool = False, prior_site_re_sd: float = 1.0, prior_obs_re_sd: float = 1.0,
-                 prior_mu=((0.0, 10.0), (0.0, 10.0)), prior_sigma=((5.0, 1.0), (5.0, 1.0)), re_fp_mode: Optional[str] = None):
+                 prior_mu=((0.0, 10.0), (0.0, 10.0)), prior_sigma=((5.0, 1.0), (5.0, 1.0)), re_fp_mode: Optional[str] = None,
+                 ARU_obs_covs=None, ARU_obs=None, scores_obs=None, prior_fc=(2.0, 5.0), prior_fu=(2.0, 5.0)):
         lib = _ffi.load()
-        if model not in ("occu", "occu_rn", "occu_fp", "occu_cop", "nmixture", "occu_re", "occu_cs", "occu_dyn"):
+        if model not in ("occu", "occu_rn", "occu_fp", "occu_cop", "nmixture", "occu_re", "occu_cs", "occu_dyn", "occu_comb"):
             raise ValueError(f"unknown model {model!r}")
         if fp_mode not in ("constant", "unoccupied") and not (model == "occu_cop" and fp_mode is None):
             raise ValueError(f"unknown fp_mode {fp_mode!r}")
@@ -157,7 +158,29 @@ class OccuDataset:
         pb = _ffi.bl_normal_prior(float(prior_beta[0]), float(prior_beta[1]))
         pa = _ffi.bl_normal_prior(float(prior_alpha[0]), float(prior_alpha[1]))
         h = C.c_void_p()
-        if model == "occu_dyn":
+        if model == "occu_comb":
+            # obs_covs / obs are the point counts' (one species); theta = [beta | alpha_PC | alpha_ARU | logit fc | logit fu | mu0 |
+            # log(mu1 - mu0) | log sigma0 | log sigma1] (include/biolith_hip.h: bl_dataset_create_comb)
+            if self.S != 1:
+                raise NotImplementedError("occu_comb: one species per dataset")
+            Wa = np.ascontiguousarray(ARU_obs_covs, dtype=np.float32)
+            Ya = np.ascontiguousarray(ARU_obs, dtype=np.float32)
+            Sc = np.ascontiguousarray(scores_obs, dtype=np.float32)
+            if Wa.ndim != 4 or Wa.shape[:2] != (N, T):
+                raise ValueError("ARU_obs_covs must be of shape (n_sites, n_periods, ARU_replicates, n_ARU_obs_covs)")
+            if Ya.shape != (1, N, T, Wa.shape[2]):
+                raise ValueError("ARU_obs must have shape (1, n_sites, n_periods, ARU_replicates)")
+            if Sc.ndim != 4 or Sc.shape[:3] != (1, N, T):
+                raise ValueError("scores_obs must have shape (1, n_sites, n_periods, scores_replicates)")
+            self.dims_comb = _ffi.bl_comb_dims(N, T, J, Wa.shape[2], Sc.shape[3], Ks, Ko, Wa.shape[3])
+            self.Ka, self.Ja, self.Js = Wa.shape[3], Wa.shape[2], Sc.shape[3]
+            pfc, pfu = _ffi.bl_beta_prior(*map(float, prior_fc)), _ffi.bl_beta_prior(*map(float, prior_fu))
+            pm = np.ascontiguousarray(np.asarray(prior_mu, dtype=np.float64).reshape(4))
+            ps = np.ascontiguousarray(np.asarray(prior_sigma, dtype=np.float64).reshape(4))
+            _ffi.check(lib.bl_dataset_create_comb(C.byref(self.dims_comb), _fp(X), _fp(W), _fp(Y), _fp(Wa), _fp(Ya), _fp(Sc),
+                                                  C.byref(pfc), C.byref(pfu), _dp(pm), _dp(ps), C.byref(pb), C.byref(pa), device, C.byref(h)))
+            self.D = Ks + Ko + Wa.shape[3] + 9
+        elif model == "occu_dyn":
             # builder-defined dynamic occupancy (no reference counterpart): theta = [b_psi | b_gamma | b_eps (Ks+1 each) | alpha (Ko+1)]
             if self.S != 1:
                 raise NotImplementedError("occu_dyn: one species per dataset")

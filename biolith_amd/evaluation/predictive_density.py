@@ -59,6 +59,8 @@ def log_likelihood(model_fn: Callable, posterior_samples: Dict[str, np.ndarray],
     >>> preds = predict(occu, results.mcmc, **data)
     >>> log_likelihood(occu, preds, **data)
     """
+    if getattr(model_fn, "__biolith_amd_model__", None) == "occu_comb":
+        raise NotImplementedError("log_likelihood / lppd / waic: not built for occu_comb (its three observed sites are a later addition)")
     ps = {k: v for k, v in posterior_samples.items() if k not in observation_keys}
     obs = np.asarray(kwargs["obs"], dtype=np.float32)
     valid = _valid_obs(kwargs["site_covs"], kwargs["obs_covs"], obs).transpose((3, 2, 1, 0))  # (J, T, N, S)

@@ -114,6 +114,10 @@ def fit(
                 count, first = shard_chains(num_chains, world, r)
                 if count == 0:
                     continue
+                if spec.model == "occu_comb":
+                    jobs.append(_comb_job(spec, sp, dev, strategy, dict(num_warmup=num_warmup, num_samples=num_samples, num_chains=count,
+                                                                         seed=random_seed, chain_offset=chain_offset + sp * num_chains + first)))
+                    continue
                 ds = OccuDataset(spec.site_covs, spec.obs_covs, spec.obs if joint else spec.obs[sp:sp + 1], spec.prior_beta, spec.prior_alpha,
                                  device=dev, model=spec.model, **engine_options(spec))
                 kw = dict(num_warmup=num_warmup, num_samples=num_samples, num_chains=count,
@@ -289,6 +293,9 @@ def fit(
             for i, name in enumerate(site_names):
                 samples[f"{prefix}{name}"] = block[..., i]
         return FitResult(samples, mcmc)
+    if spec.model == "occu_comb":
+        mcmc = _assemble_comb(per_species, spec, num_warmup)
+        return FitResult(rename_samples(mcmc.get_samples(), site_names, None), mcmc)
     mcmc = _assemble(per_species, spec, num_warmup, joint_result)
     samples = rename_samples(mcmc.get_samples(), site_names, obs_names)
     return FitResult(samples, mcmc)
@@ -313,6 +320,99 @@ def engine_options(spec) -> dict:
     if spec.model == "occu_cs":
         opts.update(prior_mu=spec.extras["prior_mu"], prior_sigma=spec.extras["prior_sigma"])
     return opts
+
+
+def _comb_job(spec, sp, device, strategy, kw):
+    """occu_comb: species ``sp`` as a launch of its own (nothing is shared across the species plate, occu_comb.py:224-248, so the
+    joint posterior factorises).  theta = [beta | alpha_PC | alpha_ARU | logit fc | logit fu | mu0 | log(mu1 - mu0) | log sigma0 |
+    log sigma1]."""
+    from ..engine import OccuDataset
+    from .init import comb_initial_positions
+
+    ex = spec.extras
+    ds = OccuDataset(spec.site_covs, spec.obs_covs, spec.obs[sp:sp + 1], spec.prior_beta, spec.prior_alpha, device=device, model="occu_comb",
+                     ARU_obs_covs=ex["ARU_obs_covs"], ARU_obs=ex["ARU_obs"][sp:sp + 1], scores_obs=ex["scores_obs"][sp:sp + 1],
+                     prior_fc=ex["prior_fc"], prior_fu=ex["prior_fu"], prior_mu=ex["prior_mu"], prior_sigma=ex["prior_sigma"])
+    init = comb_initial_positions(strategy, Ks=ds.Ks, Kpc=ds.Ko, Karu=ds.Ka, num_chains=kw["num_chains"], first_chain=kw["chain_offset"],
+                                  seed=kw["seed"], species=sp)
+    if init is not None:
+        kw["init_theta"] = init
+    return sp, ds, kw
+
+
+def _assemble_comb(per_species, spec, num_warmup) -> HipMCMC:
+    """occu_comb: draws (C, S, D) per species -> the reference's sample sites (occu_comb.py:224-349), the species plate last.
+    psi and the detection probabilities are formed here from the draws (the engine's bl_deterministic does not serve this model)."""
+    ds0, res0 = per_species[0]
+    C, S, D = res0.draws.shape
+    Ks, Kp, Ka = ds0.Ks, ds0.Ko, ds0.Ka
+    nsp = len(per_species)
+    dr = np.stack([r.draws for _, r in per_species], axis=2)                      # (C, S, nsp, D)
+    o = Ks + Kp + Ka + 3
+    e = dr[..., o:].astype(np.float64)
+    latent = dict(beta=dr[..., :Ks + 1], alpha_PC=dr[..., Ks + 1: Ks + Kp + 2], alpha_ARU=dr[..., Ks + Kp + 2: o])
+    latent["ARU_prob_fp_constant"] = (1.0 / (1.0 + np.exp(-e[..., 0]))).astype(np.float32)
+    latent["ARU_fp_unoccupied"] = (1.0 / (1.0 + np.exp(-e[..., 1]))).astype(np.float32)
+    latent["mu0"] = e[..., 2].astype(np.float32)
+    latent["mu1"] = (e[..., 2] + np.exp(e[..., 3])).astype(np.float32)
+    latent["sigma0"], latent["sigma1"] = np.exp(e[..., 4]).astype(np.float32), np.exp(e[..., 5]).astype(np.float32)
+    T = spec.obs_covs.shape[1]
+
+    def sigmoid(lin):
+        return (1.0 / (1.0 + np.exp(-lin))).astype(np.float32)
+
+    def psi():
+        X = np.nan_to_num(spec.site_covs.astype(np.float32))
+        b = latent["beta"]                                                          # (C, S, nsp, Ks + 1)
+        lin = b[..., :1] + b[..., 1:] @ X.T                                         # (C, S, nsp, N)
+        p = sigmoid(np.moveaxis(lin, 2, -1))                                        # (C, S, N, nsp)
+        return np.ascontiguousarray(np.broadcast_to(p[:, :, None], (C, S, T) + p.shape[2:]))
+
+    def detection(name, covs):
+        def get():
+            W = np.nan_to_num(np.asarray(covs, dtype=np.float32)).transpose(2, 1, 0, 3)   # (J, T, N, K)
+            a = latent[name]                                                        # (C, S, nsp, K + 1)
+            lin = np.einsum("jtnk,cspk->csjtnp", W, a[..., 1:]) + a[..., 0][:, :, None, None, None, :]
+            return sigmoid(lin)                                                     # (C, S, J, T, N, nsp)
+        return get
+
+    def prob_detection_fp():
+        # occu_comb.py:325-331: 1 - (1 - z p)(1 - fc)(1 - (1 - z) fu), with z's enumeration axis in front of the plates (as occu's
+        # prob_detection_fp here): index 0 = unoccupied, 1 = occupied
+        p = detection("alpha_ARU", spec.extras["ARU_obs_covs"])()
+        fc = latent["ARU_prob_fp_constant"][:, :, None, None, None, :]
+        fu = latent["ARU_fp_unoccupied"][:, :, None, None, None, :]
+        z0 = np.broadcast_to(1.0 - (1.0 - fc) * (1.0 - fu), p.shape).astype(np.float32)
+        z1 = (1.0 - (1.0 - p) * (1.0 - fc)).astype(np.float32)
+        return np.stack([z0, z1], axis=2)
+
+    import copy
+
+    res = copy.copy(res0)
+    if nsp > 1:
+        res.diverging = np.logical_or.reduce([r.diverging for _, r in per_species])
+        res.num_steps = np.sum([r.num_steps for _, r in per_species], axis=0)
+        res.accept_prob = np.mean([r.accept_prob for _, r in per_species], axis=0)
+        res.potential_energy = np.sum([r.potential_energy for _, r in per_species], axis=0)
+        res.n_leapfrog = np.sum([r.n_leapfrog for _, r in per_species], axis=0)
+        res.kernel_ms = float(np.sum([r.kernel_ms for _, r in per_species]))
+        res.inv_mass = np.concatenate([r.inv_mass for _, r in per_species], axis=1)
+        res.draws = np.concatenate([r.draws for _, r in per_species], axis=2)
+    return HipMCMC(res, latent=latent,
+                   deterministic=dict(psi=_memo(psi), PC_prob_detection=_memo(detection("alpha_PC", spec.obs_covs)),
+                                      ARU_prob_detection=_memo(detection("alpha_ARU", spec.extras["ARU_obs_covs"])),
+                                      ARU_prob_detection_fp=_memo(prob_detection_fp)),
+                   num_warmup=num_warmup, spec_shape=spec.shape)
+
+
+def _memo(fn):   # a site is computed once, on its first access
+    box = []
+
+    def get():
+        if not box:
+            box.append(fn())
+        return box[0]
+    return get
 
 
 def _concat_chains(parts):

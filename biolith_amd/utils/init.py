@@ -127,3 +127,63 @@ def initial_positions(strategy: Optional[InitStrategy], *, D: int, Ks: int, Ko: 
                     col = np.median(_prior_draws(rng, prior, (n, width)), axis=0)
                 out[c, s * Dsp + off: s * Dsp + off + width] = col
     return out
+
+
+def comb_initial_positions(strategy: Optional[InitStrategy], *, Ks: int, Kpc: int, Karu: int, num_chains: int, first_chain: int,
+                           seed: int, species: int = 0):
+    """``initial_positions`` for occu_comb (one species per launch): theta = [beta | alpha_PC | alpha_ARU | logit fc | logit fu | mu0 |
+    log(mu1 - mu0) | log sigma0 | log sigma1].  ``init_to_value`` takes the reference's site names with constrained values
+    (``ARU_prob_fp_constant``, ``ARU_fp_unoccupied``, ``mu0``, ``mu1``, ``sigma0``, ``sigma1``: a scalar, or one value per species;
+    the coefficients as ``(n_species, K + 1)`` or one row); everything not named starts as ``init_to_uniform``."""
+    if strategy is None or (strategy.kind == "uniform" and strategy.radius == 2.0):
+        return None
+    if strategy.kind not in ("uniform", "feasible", "value"):
+        raise NotImplementedError(f"init_to_{strategy.kind}: built for models whose coordinates are all regression coefficients "
+                                  "(no false-positive rate, random effects or score parameters); use init_to_uniform / _feasible / _value")
+    o = Ks + Kpc + Karu + 3
+    D = o + 6
+    blocks = dict(beta=(0, Ks + 1), alpha_PC=(Ks + 1, Kpc + 1), alpha_ARU=(Ks + Kpc + 2, Karu + 1))
+    scalars = ("ARU_prob_fp_constant", "ARU_fp_unoccupied", "mu0", "mu1", "sigma0", "sigma1")
+    vals = {k: np.asarray(v, dtype=np.float64) for k, v in strategy.values.items()}
+    unknown = set(vals) - set(blocks) - set(scalars)
+    if unknown:
+        raise NotImplementedError(f"init_to_value: sites {sorted(unknown)} are not sampled sites of occu_comb")
+
+    def scalar(name):
+        v = vals[name]
+        return float(v.reshape(-1)[species] if v.size > 1 else v.reshape(()))
+
+    out = np.empty((num_chains, D), dtype=np.float64)
+    for c in range(num_chains):
+        rng = np.random.default_rng([int(seed) & 0x7FFFFFFF, first_chain + c, 0x1B1D])
+        if strategy.kind == "feasible":
+            out[c] = 0.0
+            continue
+        out[c] = rng.uniform(-strategy.radius if strategy.kind == "uniform" else -2.0, strategy.radius if strategy.kind == "uniform" else 2.0, size=D)
+        for name, (off, width) in blocks.items():
+            if name in vals:
+                v = vals[name]
+                row = v if v.ndim == 1 else v[species]
+                if row.shape != (width,):
+                    raise ValueError(f"init_to_value: {name} must have {width} coefficients per species, got shape {v.shape}")
+                out[c, off: off + width] = row
+        for k, name in enumerate(("ARU_prob_fp_constant", "ARU_fp_unoccupied")):
+            if name in vals:
+                f = scalar(name)
+                if not 0.0 < f < 1.0:
+                    raise ValueError(f"init_to_value: {name} must lie in (0, 1)")
+                out[c, o + k] = np.log(f) - np.log1p(-f)
+        if "mu0" in vals:
+            out[c, o + 2] = scalar("mu0")
+        if "mu1" in vals:
+            gap = scalar("mu1") - out[c, o + 2]
+            if not gap > 0.0:
+                raise ValueError("init_to_value: mu1 must exceed mu0 (its prior is truncated below at mu0)")
+            out[c, o + 3] = np.log(gap)
+        for k, name in enumerate(("sigma0", "sigma1")):
+            if name in vals:
+                sd = scalar(name)
+                if not sd > 0.0:
+                    raise ValueError(f"init_to_value: {name} must be positive")
+                out[c, o + 4 + k] = np.log(sd)
+    return out

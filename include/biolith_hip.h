@@ -204,6 +204,31 @@ int bl_dataset_create_cs(const bl_dims *dims, const float *site_covs, const floa
                          const double *prior_mu, const double *prior_sigma, const bl_normal_prior *prior_beta,
                          const bl_normal_prior *prior_alpha, int device, bl_dataset **out);
 /*
+ * The combined point-count / ARU / score occupancy model biolith.models.occu_comb (models/occu_comb.py:19-349), one species
+ * per handle.  Per (site, period) one enumerated z ~ Bernoulli(psi) is shared by three blocks of replicates:
+ *   point counts  pc_obs [N][T][Jpc]     y ~ Bernoulli(z p_pc)                       (no false positives),
+ *   ARU           aru_obs [N][T][Jaru]   y ~ Bernoulli(1 - (1 - z p_aru)(1 - fc)(1 - (1 - z) fu)),
+ *   scores        scores [N][T][Js]      s ~ Normal(z ? mu1 : mu0, z ? sigma1 : sigma0),
+ * p_pc = sigmoid(alpha_PC . (1, pc_covs [N][T][Jpc][Kpc])), p_aru likewise with aru_covs [N][T][Jaru][Karu].  NaN = missing: a
+ * visit is masked where its y, any of its block's covariates or any site covariate is NaN; a score where it or a site covariate is.
+ * Every Bernoulli probability is clamped to [tiny, 1 - eps] as NumPyro clamps it (a point-count detection at z = 0 costs log tiny).
+ * theta (NumPyro's unconstrained space), D = (Ks + 1) + (Kpc + 1) + (Karu + 1) + 6:
+ *   [beta (Ks+1) | alpha_PC (Kpc+1) | alpha_ARU (Karu+1) | logit fc | logit fu | mu0 | log(mu1 - mu0) | log sigma0 | log sigma1]
+ * with fc ~ Beta(prior_fc), fu ~ Beta(prior_fu), mu0 ~ Normal(prior_mu[0..1]), mu1 ~ Normal(prior_mu[2..3]) truncated below at mu0,
+ * sigma_f ~ Gamma(prior_sigma[2f], prior_sigma[2f+1]); beta ~ prior_beta, both alphas ~ prior_alpha (bl_dataset_set_prior_family
+ * applies).  At most 16 covariates per block.  bl_logp_grad and bl_nuts_* serve the handle (the random-effects kernels' framework);
+ * bl_deterministic / bl_predict* do not: psi and the detection probabilities are formed by the caller from the draws.
+ */
+typedef struct bl_comb_dims {
+    int32_t n_sites, n_periods;           /* N, T                                          */
+    int32_t n_pc, n_aru, n_scores;        /* Jpc, Jaru, Js: replicates of each block       */
+    int32_t n_site_covs, n_pc_covs, n_aru_covs; /* Ks, Kpc, Karu                            */
+} bl_comb_dims;
+int bl_dataset_create_comb(const bl_comb_dims *dims, const float *site_covs, const float *pc_covs, const float *pc_obs,
+                           const float *aru_covs, const float *aru_obs, const float *scores, const bl_beta_prior *prior_fc,
+                           const bl_beta_prior *prior_fu, const double *prior_mu, const double *prior_sigma,
+                           const bl_normal_prior *prior_beta, const bl_normal_prior *prior_alpha, int device, bl_dataset **out);
+/*
  * The other prior family biolith.utils.grid_search_priors tries for the regression coefficients
  * (utils/grid_search.py:366-371): Laplace(loc, scale) instead of Normal(loc, scale), per side, with the (loc, scale) the
  * dataset was created with.  Call between bl_dataset_create* and the first use; applies to every model.
@@ -214,7 +239,7 @@ int bl_dataset_set_prior_family(bl_dataset *ds, int family_beta, int family_alph
 int bl_dataset_destroy(bl_dataset *ds);
 /* Coordinates of theta.  occu / occu_rn / nmixture / occu_cop without a rate: D = Ks+1 + Ko+1, theta = [beta_0..beta_Ks,
  * alpha_0..alpha_Ko]; with a false-positive coordinate (bl_dataset_create_fp, occu_cop with a rate): + 1 (trailing phi);
- * S species under one chain: S (Ks + Ko + 2) (+ 1); dynamic occupancy: 3 (Ks + 1) + Ko + 1; occu_cs: Ks + Ko + 6; random
+ * S species under one chain: S (Ks + Ko + 2) (+ 1); dynamic occupancy: 3 (Ks + 1) + Ko + 1; occu_cs: Ks + Ko + 6; occu_comb: Ks + Kpc + Karu + 9; random
  * effects: Ks + Ko + 2 + the log sds + 2 N (site effects) + N T J (observation effects), per species where S > 1. */
 int bl_dataset_param_dim(const bl_dataset *ds, int *D);
 
