@@ -19,6 +19,8 @@
 #include "logp_kernel.hpp"
 #include "re_kernel.hpp"
 #include "nuts_kernel.hpp"
+#include "pred_rng.hpp"
+#include "site_posterior.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -295,30 +297,7 @@ extern "C" int bl_device_count(int *count)
 }
 
 // ------------------------------------------------------------------ posterior predictive ----
-// One generator per (draw, period, site): xoshiro128++ keyed by splitmix64 of the flat index, so the
-// sample does not depend on the launch geometry or on how the draws are chunked.
-__device__ inline unsigned long long bl_splitmix(unsigned long long &x)
-{
-    unsigned long long z = (x += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-struct BlPredRng {
-    unsigned s0, s1, s2, s3;
-    __device__ BlPredRng(unsigned long long seed, unsigned long long index)
-    {
-        unsigned long long x = seed ^ (index * 0xD1342543DE82EF95ull);
-        const unsigned long long a = bl_splitmix(x), b = bl_splitmix(x);
-        s0 = (unsigned)a; s1 = (unsigned)(a >> 32); s2 = (unsigned)b; s3 = (unsigned)(b >> 32) | 1u;
-    }
-    __device__ float uniform() // [0, 1)
-    {
-        const unsigned r0 = s0 + s3, r = ((r0 << 7) | (r0 >> 25)) + s0, t = s1 << 9;
-        s2 ^= s0; s3 ^= s1; s1 ^= s2; s0 ^= s3; s2 ^= t; s3 = (s3 << 11) | (s3 >> 21);
-        return (float)(r >> 8) * 5.9604644775390625e-08f;
-    }
-};
+// (the generator, one per (draw, period, site): pred_rng.hpp)
 // occu (occu.py:207-241 with obs=None):  z ~ Bernoulli(psi),  y_j ~ Bernoulli(z * p_j)
 // occu_rn (occu_rn.py:192-221):          N ~ Categorical(Poisson(lambda) pmf on 0..K),  y_j ~ Bernoulli(1 - (1 - r_j)^N)
 __global__ void bl_predict_kernel(const float *__restrict__ rows, const float *__restrict__ wraw, int n_stride, int N, int T, int J,
@@ -426,6 +405,72 @@ extern "C" int bl_predict(bl_dataset *ds, int n_draws, const float *draws, uint6
         BL_HIP(hipGetLastError());
         if (latent) BL_HIP(hipMemcpy(latent + (size_t)n0 * T * N, d_lat, (size_t)(n1 - n0) * T * N, hipMemcpyDeviceToHost));
         if (y) BL_HIP(hipMemcpy(y + (size_t)n0 * J * T * N, d_y, (size_t)(n1 - n0) * J * T * N, hipMemcpyDeviceToHost));
+    }
+    return BL_OK;
+}
+
+// ---- conditional occupancy: P(z | data), the site-period log-likelihood and a draw of z, per posterior draw ----
+// (BUILDER-DEFINED: the reference's predict withholds the observations.)  Kernel: site_posterior.hip.  The sign-folded visit rows the
+// density kernels read already carry y and the mask, so nothing is uploaded; a draw's layout is bl_predict's.
+extern "C" int bl_site_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *z_prob, uint8_t *z)
+{
+    if (!ds || !draws || n_draws <= 0 || (!log_lik && !z_prob && !z)) return bl_fail(BL_ERR_INVALID, "bl_site_posterior: bad argument");
+    if (ds->nsp > 1) return bl_fail(BL_ERR_UNSUPPORTED, "bl_site_posterior: a joint-species handle samples; use one handle per species");
+    const char *refused = nullptr;
+    if (ds->model == 1) refused = "occu_rn";
+    else if (ds->model == 3) refused = "occu_cop";
+    else if (ds->model == 4) refused = "nmixture";
+    else if (ds->model == 8) refused = "occu_dyn";
+    else if (ds->model == 6) {
+        const int k = ds->re.kind;
+        refused = k == 1 ? "occu_cs" : k == 3 ? "nmixture" : (k == 4 || k == 5) ? "occu_rn" : (k == 6 || k == 7) ? "occu_cop" : nullptr;
+    } else if (ds->model != 0 && ds->model != 2) refused = "this model";
+    if (refused)
+        return bl_fail(BL_ERR_UNSUPPORTED, "bl_site_posterior: not built for %s (occu, with or without false positives / random effects, and occu_comb)", refused);
+    if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
+    int rc = set_device(ds);
+    if (rc) return rc;
+    const int N = ds->dims.n_sites, T = ds->dims.n_periods, D = ds->D;
+    BlSitePostParams p{};
+    p.ns = ds->n_stride; p.N = N; p.T = T; p.Ks = ds->Ks; p.D = D; p.seed = (unsigned long long)seed;
+    p.o_u = p.o_v = p.o_e = p.o_fp = -1; p.r_per = p.o_x = 0;
+    if (ds->model == 6 && ds->re.kind == 8) { // occu_comb: its own rows (bl_dataset_create_comb)
+        const BlReModel &m = ds->re;
+        const BlCombModel &cm = ds->comb;
+        p.rows = m.rows; p.comb = 1;
+        p.a = BlSitePostBlock{m.rv0, cm.Jpc, cm.Kpc, cm.Kpc + 1, m.Ks + 1};
+        p.b = BlSitePostBlock{m.rv0 + cm.r_aru, cm.Jaru, cm.Karu, cm.Karu + 1, m.Ks + cm.Kpc + 2};
+        p.r_per = m.rv0 + cm.r_per; p.o_x = m.G0;
+    } else {
+        const int Ko = ds->model == 6 ? ds->re.Ko : ds->Ko;
+        p.rows = ds->d_rows;
+        p.a = BlSitePostBlock{ds->KS, ds->dims.n_replicates, Ko, ds->KO + 1, ds->Ks + 1};
+        p.b = BlSitePostBlock{0, 0, 0, 1, 0};
+        if (ds->model == 2) { p.fp_mode = ds->fp_mode; p.o_fp = D - 1; }
+        if (ds->model == 6) {
+            const BlReModel &m = ds->re;
+            if (m.kind == 2) { p.fp_mode = m.fp_mode; p.o_fp = m.o_fp; }
+            p.o_u = m.o_u; p.o_v = m.o_v; p.o_e = m.o_e;
+        }
+    }
+    float *d_draws = nullptr, *d_ll = nullptr, *d_q = nullptr;
+    unsigned char *d_z = nullptr;
+    DevScratch scratch;
+    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * D * 4));
+    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * D * 4, hipMemcpyHostToDevice));
+    const size_t cells = (size_t)T * N; // per draw; the larger outputs are 4 bytes a cell
+    int chunk = (int)std::min<size_t>((size_t)n_draws, std::max<size_t>(1, ((size_t)256 << 20) / (cells * 4)));
+    if (log_lik) BL_HIP(scratch.alloc((void **)&d_ll, (size_t)chunk * cells * 4));
+    if (z_prob) BL_HIP(scratch.alloc((void **)&d_q, (size_t)chunk * cells * 4));
+    if (z) BL_HIP(scratch.alloc((void **)&d_z, (size_t)chunk * cells));
+    p.draws = d_draws; p.log_lik = d_ll; p.z_prob = d_q; p.z = d_z;
+    for (int n0 = 0; n0 < n_draws; n0 += chunk) {
+        const int n1 = (n0 + chunk < n_draws) ? n0 + chunk : n_draws;
+        p.n0 = n0; p.n1 = n1;
+        BL_HIP((hipError_t)bl_launch_site_posterior(&p, (n1 - n0) < 1024 ? (n1 - n0) : 1024, nullptr));
+        if (log_lik) BL_HIP(hipMemcpy(log_lik + (size_t)n0 * cells, d_ll, (size_t)(n1 - n0) * cells * 4, hipMemcpyDeviceToHost));
+        if (z_prob) BL_HIP(hipMemcpy(z_prob + (size_t)n0 * cells, d_q, (size_t)(n1 - n0) * cells * 4, hipMemcpyDeviceToHost));
+        if (z) BL_HIP(hipMemcpy(z + (size_t)n0 * cells, d_z, (size_t)(n1 - n0) * cells, hipMemcpyDeviceToHost));
     }
     return BL_OK;
 }

@@ -1,0 +1,167 @@
+// site_posterior.hip -- the kernel of bl_site_posterior: per posterior draw and (period, site) the z-marginalised log-likelihood
+// l = logaddexp(A, B), the conditional occupancy probability q = sigmoid(A - B) and one draw z ~ Bernoulli(q), with
+//   A = log psi + log p(obs | z = 1),  B = log(1 - psi) + log p(obs | z = 0)
+// as the density kernels define them (occu_device.hpp: bl_eval_sites_hbm / _fp; re_kernel.hpp: bl_re_site_pass, bl_comb_site_pass):
+// the same terms, the same clamps (a detection at z = 0 without a false-positive rate costs log tiny; occu_comb's z = 0 ARU
+// probability is clamped to [tiny, 1 - eps]), the same masks (c = 0 in a visit's record, n = 0 in a period's score row).
+//
+// One thread per site, the draws on grid.y: a visit row is read by 64 neighbouring sites at once, a draw's coefficients are
+// wave-uniform.  Nothing is kept per covariate: the rows are read where they are used (the data set is L2-resident), so no array
+// with a run-time index exists and nothing goes to scratch.  The z = 1 sum is Kahan-compensated and log(1 + e) keeps its low bits,
+// so that a cell's error stays a few ulps of its largest term however many visits it has.
+#include "site_posterior.hpp"
+
+#include "nuts_kernel.hpp"
+#include "pred_rng.hpp"
+
+namespace {
+
+constexpr float SP_LOG_TINY = -87.33654475f, SP_TINY = 1.1754944e-38f, SP_LOG_EPS = -15.9423847f, SP_HL2PI = 0.9189385f;
+
+// log(1 + e) for 0 <= e <= 1, relative error of a few ulps also where e is small (log(op) e / (op - 1): the rounding of 1 + e cancels)
+__device__ __forceinline__ float sp_log1p(float e)
+{
+    const float op = 1.0f + e, d = op - 1.0f;
+    const float r = bl_log(op) * (e * bl_rcp(d));
+    return d == 0.0f ? e : r;
+}
+struct SpSum { // Kahan
+    float s = 0.0f, c = 0.0f;
+    __device__ __forceinline__ void add(float x)
+    {
+        const float y = x - c, t = s + y;
+        c = (t - s) - y;
+        s = t;
+    }
+};
+// f = sigmoid(phi): f, 1 - f, log f, log(1 - f)
+__device__ __forceinline__ void sp_rate(float phi, float &f, float &g, float &lf, float &l1f)
+{
+    const float e = bl_exp(-fabsf(phi)), l = sp_log1p(e), r = bl_rcp(1.0f + e);
+    f = (phi > 0.0f ? 1.0f : e) * r;
+    g = (phi > 0.0f ? e : 1.0f) * r;
+    lf = fminf(phi, 0.0f) - l;
+    l1f = -fmaxf(phi, 0.0f) - l;
+}
+
+} // namespace
+
+template <bool COMB>
+__global__ void bl_site_posterior_kernel(const BlSitePostParams p)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= p.N) return;
+    const float *__restrict__ rows = p.rows;
+    const int ns = p.ns, N = p.N, T = p.T;
+    for (int n = p.n0 + blockIdx.y; n < p.n1; n += gridDim.y) {
+        const float *__restrict__ th = p.draws + (size_t)n * p.D;
+        float eta = th[0];
+        for (int k = 0; k < p.Ks; k++) eta = fmaf(rows[(size_t)k * ns + i], th[k + 1], eta);
+        if (p.o_u >= 0) eta += th[p.o_u + i];
+        const float vi = p.o_v >= 0 ? th[p.o_v + i] : 0.0f;
+        const float ee = bl_exp(-fabsf(eta)), lop = sp_log1p(ee);
+        const float log_psi = fminf(eta, 0.0f) - lop, log_1mpsi = fminf(-eta, 0.0f) - lop;
+        const float psi = (eta > 0.0f ? 1.0f : ee) * bl_rcp(1.0f + ee);
+        // the draw's scalars: what a detection / a non-detection of block a costs at z = 0, the rate that acts at z = 1
+        float f1 = 0.0f, l1f1 = 0.0f, z0_det = SP_LOG_TINY, z0_non = 0.0f;
+        float fc = 0.0f, lgc = 0.0f, lp0 = 0.0f, lq0 = 0.0f, mu0 = 0.0f, mu1 = 0.0f, c0 = 0.0f, c1 = 0.0f, is0 = 0.0f, is1 = 0.0f;
+        if constexpr (COMB) {
+            float gc, fu, gu, lfc, lfu, lgu;
+            sp_rate(th[p.o_x], fc, gc, lfc, lgc);
+            sp_rate(th[p.o_x + 1], fu, gu, lfu, lgu);
+            lp0 = bl_log(fmaxf(fmaf(fu, gc, fc), SP_TINY)); // p0 = 1 - (1 - fc)(1 - fu), clamped to [tiny, 1 - eps]
+            lq0 = fmaxf(lgc + lgu, SP_LOG_EPS);
+            mu0 = th[p.o_x + 2]; mu1 = mu0 + bl_exp(th[p.o_x + 3]);
+            c0 = th[p.o_x + 4] + SP_HL2PI; c1 = th[p.o_x + 5] + SP_HL2PI;              // log sigma + log(2 pi) / 2
+            is0 = bl_exp(-2.0f * th[p.o_x + 4]); is1 = bl_exp(-2.0f * th[p.o_x + 5]);  // 1 / sigma^2
+        } else if (p.fp_mode) {
+            float f, g;
+            sp_rate(th[p.o_fp], f, g, z0_det, z0_non);
+            if (p.fp_mode == 1) { f1 = f; l1f1 = z0_non; }
+        }
+        for (int t = 0; t < T; t++) {
+            SpSum a1;
+            a1.add(log_psi);
+            float nd = 0.0f, nn = 0.0f; // unmasked detections / non-detections of block a
+            const float *__restrict__ al = th + p.a.o_al;
+            for (int j = 0; j < p.a.J; j++) {
+                const int v = t * p.a.J + j;
+                const size_t r = (size_t)(p.a.r0 + v * p.a.vw) * ns + i;
+                const float c = rows[r];
+                if (c == 0.0f) continue; // masked
+                float u = c * al[0];
+                for (int k = 1; k <= p.a.K; k++) u = fmaf(rows[r + (size_t)k * ns], al[k], u);
+                if constexpr (!COMB) {
+                    float re = vi;
+                    if (p.o_e >= 0) re += th[(size_t)p.o_e + (size_t)i * T * p.a.J + v];
+                    u = fmaf(c, re, u);
+                }
+                const float e = bl_exp(-fabsf(u)), lsu = fminf(u, 0.0f) - sp_log1p(e); // log sigma(u)
+                if (c > 0.0f) {
+                    nd += 1.0f;
+                    if (f1 > 0.0f) { // log(p + f (1 - p))
+                        const float rop = bl_rcp(1.0f + e);
+                        a1.add(bl_log(fmaf(f1, (u > 0.0f ? e : 1.0f) * rop, (u > 0.0f ? 1.0f : e) * rop)));
+                    } else
+                        a1.add(lsu);
+                } else {
+                    nn += 1.0f;
+                    a1.add(lsu);
+                }
+            }
+            a1.add(nn * l1f1);
+            float B = log_1mpsi + fmaf(nd, z0_det, nn * z0_non);
+            float nobs = nd + nn;
+            if constexpr (COMB) {
+                float ad = 0.0f, an = 0.0f;
+                const float *__restrict__ aar = th + p.b.o_al;
+                for (int j = 0; j < p.b.J; j++) {
+                    const size_t r = (size_t)(p.b.r0 + (t * p.b.J + j) * p.b.vw) * ns + i;
+                    const float c = rows[r];
+                    if (c == 0.0f) continue;
+                    float u = c * aar[0];
+                    for (int k = 1; k <= p.b.K; k++) u = fmaf(rows[r + (size_t)k * ns], aar[k], u);
+                    const float e = bl_exp(-fabsf(u));
+                    if (c > 0.0f) { // log(p + fc (1 - p))
+                        const float rop = bl_rcp(1.0f + e);
+                        ad += 1.0f;
+                        a1.add(bl_log(fmaf(fc, (u > 0.0f ? e : 1.0f) * rop, (u > 0.0f ? 1.0f : e) * rop)));
+                    } else {        // log(1 - p) + log(1 - fc)
+                        an += 1.0f;
+                        a1.add(fminf(u, 0.0f) - sp_log1p(e));
+                    }
+                }
+                a1.add(an * lgc);
+                // the period's unmasked scores as count, mean and sum of squared deviations: sum log N(s; mu, sigma) without per-score work
+                const size_t rp = (size_t)(p.r_per + 6 * t) * ns + i;
+                const float sc_n = rows[rp + (size_t)3 * ns], sc_m = rows[rp + (size_t)4 * ns], sc_m2 = rows[rp + (size_t)5 * ns];
+                const float d1 = sc_m - mu1, d0 = sc_m - mu0;
+                const float q1 = fmaf(sc_n * d1, d1, sc_m2) * is1, q0 = fmaf(sc_n * d0, d0, sc_m2) * is0;
+                a1.add(fmaf(-0.5f, q1, -sc_n * c1));
+                B += fmaf(ad, lp0, an * lq0) + fmaf(-0.5f, q0, -sc_n * c0);
+                nobs += ad + an + sc_n;
+            }
+            const float A = a1.s;
+            const float d = A - B, e = bl_exp(-fabsf(d));
+            float l = fmaxf(A, B) + sp_log1p(e);
+            float q = (d > 0.0f ? 1.0f : e) * bl_rcp(1.0f + e);
+            if (nobs == 0.0f) { l = 0.0f; q = psi; } // nothing observed: the cell's likelihood is 1 and the conditional is the prior
+            const size_t o = ((size_t)(n - p.n0) * T + t) * N + i;
+            if (p.log_lik) p.log_lik[o] = l;
+            if (p.z_prob) p.z_prob[o] = q;
+            if (p.z) {
+                BlPredRng rng(p.seed, ((unsigned long long)n * T + t) * N + i);
+                p.z[o] = rng.uniform() < q ? 1 : 0;
+            }
+        }
+    }
+}
+
+extern "C" int bl_launch_site_posterior(const BlSitePostParams *p, int grid_y, hipStream_t st)
+{
+    const int nt = p->N < 256 ? 64 : 256; // a small data set would idle three quarters of a 256-thread workgroup
+    const dim3 grid((p->N + nt - 1) / nt, grid_y), block(nt);
+    if (p->comb) hipLaunchKernelGGL(bl_site_posterior_kernel<true>, grid, block, 0, st, *p);
+    else hipLaunchKernelGGL(bl_site_posterior_kernel<false>, grid, block, 0, st, *p);
+    return (int)hipGetLastError();
+}

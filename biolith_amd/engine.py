@@ -484,6 +484,22 @@ class OccuDataset:
             _ffi.check(fn(self._h, n, _fp(d), C.c_uint64(int(seed) & (2 ** 64 - 1)), ptr(out_l), ptr(out_y)))
         return out_l, out_y
 
+    def site_posterior(self, draws, seed: int = 0, log_lik: bool = True, z_prob: bool = True, z: bool = True):
+        """Conditional occupancy for draws (n, D), each output (n, T, N): ``log_lik`` float32, the z-marginalised log-likelihood of a
+        (period, site)'s unmasked observations; ``z_prob`` float32 = P(z = 1 | those observations, theta); ``z`` uint8 ~
+        Bernoulli(z_prob), a function of (seed, draw, period, site).  occu (false positives, random effects) and occu_comb handles
+        (include/biolith_hip.h: bl_site_posterior); no counterpart in the reference."""
+        d = self._draw_matrix(draws)
+        n = d.shape[0]
+        out_l = self._big_empty((n, self.T, self.N)) if log_lik else None
+        out_q = self._big_empty((n, self.T, self.N)) if z_prob else None
+        out_z = np.empty((n, self.T, self.N), dtype=np.uint8) if z else None
+        if n:
+            u8 = None if out_z is None else out_z.ctypes.data_as(C.POINTER(C.c_uint8))
+            _ffi.check(self._lib.bl_site_posterior(self._h, n, _fp(d), C.c_uint64(int(seed) & (2 ** 64 - 1)), _fp(out_l), _fp(out_q), u8))
+            _PINNED.kick(self._lib)
+        return out_l, out_q, out_z
+
 
 def _predictive_scores(self, draws, seed: int = 0):
     """occu_cs: posterior predictive ``z`` (n, T, N), ``f`` (n, J, T, N) as uint8 and the scores ``s`` (n, J, T, N) float32

@@ -1,0 +1,40 @@
+"""lppd / WAIC from the z-marginalised site-period log-likelihood (host NumPy only).
+
+BUILDER-DEFINED, no counterpart in the reference: its ``lppd`` / ``waic`` (lppd.py, waic.py) take the log-likelihood of each
+replicate given a ``z`` drawn from the PRIOR, so the criterion carries the Monte Carlo noise of a latent the model's likelihood
+sums out analytically.  Here the unit is the (site, period) -- the level at which the marginal likelihood factorises -- and the
+pointwise term is ``latent["log_lik"]`` of :func:`biolith_amd.utils.conditional_occupancy`: log(psi p(obs | 1) + (1 - psi) p(obs | 0)).
+Cells without an unmasked observation (``n_obs == 0``) carry no likelihood and are left out.
+"""
+from __future__ import annotations
+
+from typing import Dict
+
+import numpy as np
+
+from .predictive_density import _pointwise
+
+
+def _cells(latent) -> np.ndarray:
+    """(draws, cells with n_obs > 0) float64 of a ``conditional_occupancy`` result."""
+    ll = np.asarray(latent["log_lik"], dtype=np.float64)
+    n_obs = np.asarray(latent["n_obs"])
+    if ll.shape[1:] != n_obs.shape:
+        raise ValueError(f"log_lik {ll.shape} and n_obs {n_obs.shape} do not belong together")
+    return ll[:, n_obs > 0]
+
+
+def lppd_marginal(latent) -> float:
+    """``sum_cells log mean_draws exp(log_lik)`` over the (period, site, species) cells with data."""
+    return _pointwise(_cells(latent))[0]
+
+
+def waic_marginal(latent) -> Dict[str, float]:
+    """``{"waic": -2 (lppd - p_waic), "p_waic", "lppd"}`` with the site-period as the unit (p_waic: the summed posterior variance)."""
+    l, p = _pointwise(_cells(latent))
+    return {"waic": -2 * (l - p), "p_waic": p, "lppd": l}
+
+
+def finite_sample_occupancy(latent) -> np.ndarray:
+    """(draws, T, S): the share of occupied sites in each conditional draw of ``z`` -- the finite-sample occupancy of Royle & Kery."""
+    return np.asarray(latent["z"], dtype=np.float64).mean(axis=2)

@@ -322,17 +322,36 @@ def engine_options(spec) -> dict:
     return opts
 
 
+def comb_dataset(spec, sp, device):
+    """The device dataset of species ``sp`` of an occu_comb ``OccuSpec`` (fit's jobs and ``latent.conditional_occupancy``)."""
+    from ..engine import OccuDataset
+
+    ex = spec.extras
+    return OccuDataset(spec.site_covs, spec.obs_covs, spec.obs[sp:sp + 1], spec.prior_beta, spec.prior_alpha, device=device, model="occu_comb",
+                       ARU_obs_covs=ex["ARU_obs_covs"], ARU_obs=ex["ARU_obs"][sp:sp + 1], scores_obs=ex["scores_obs"][sp:sp + 1],
+                       prior_fc=ex["prior_fc"], prior_fu=ex["prior_fu"], prior_mu=ex["prior_mu"], prior_sigma=ex["prior_sigma"])
+
+
+def comb_engine_draws(posterior, sp):
+    """occu_comb: the posterior's sample sites of species ``sp`` back in the engine's coordinates, (n, D) float32 -- the inverse of
+    what ``_assemble_comb`` reads out of a draw: [beta | alpha_PC | alpha_ARU | logit fc | logit fu | mu0 | log(mu1 - mu0) | log sigma0 |
+    log sigma1]."""
+    g = lambda k: np.asarray(posterior[k], dtype=np.float64)[:, sp]
+    n = g("beta").shape[0]
+    col = lambda k: g(k).reshape(n, 1)
+    logit = lambda f: np.log(np.clip(f, 1e-300, 1 - 1e-16) / (1.0 - np.clip(f, 1e-300, 1 - 1e-16)))
+    return np.concatenate([g("beta"), g("alpha_PC"), g("alpha_ARU"), logit(col("ARU_prob_fp_constant")), logit(col("ARU_fp_unoccupied")),
+                           col("mu0"), np.log(np.maximum(col("mu1") - col("mu0"), 1e-300)), np.log(col("sigma0")), np.log(col("sigma1"))],
+                          axis=1).astype(np.float32)
+
+
 def _comb_job(spec, sp, device, strategy, kw):
     """occu_comb: species ``sp`` as a launch of its own (nothing is shared across the species plate, occu_comb.py:224-248, so the
     joint posterior factorises).  theta = [beta | alpha_PC | alpha_ARU | logit fc | logit fu | mu0 | log(mu1 - mu0) | log sigma0 |
     log sigma1]."""
-    from ..engine import OccuDataset
     from .init import comb_initial_positions
 
-    ex = spec.extras
-    ds = OccuDataset(spec.site_covs, spec.obs_covs, spec.obs[sp:sp + 1], spec.prior_beta, spec.prior_alpha, device=device, model="occu_comb",
-                     ARU_obs_covs=ex["ARU_obs_covs"], ARU_obs=ex["ARU_obs"][sp:sp + 1], scores_obs=ex["scores_obs"][sp:sp + 1],
-                     prior_fc=ex["prior_fc"], prior_fu=ex["prior_fu"], prior_mu=ex["prior_mu"], prior_sigma=ex["prior_sigma"])
+    ds = comb_dataset(spec, sp, device)
     init = comb_initial_positions(strategy, Ks=ds.Ks, Kpc=ds.Ko, Karu=ds.Ka, num_chains=kw["num_chains"], first_chain=kw["chain_offset"],
                                   seed=kw["seed"], species=sp)
     if init is not None:

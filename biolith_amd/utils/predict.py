@@ -17,6 +17,48 @@ from .data import prepare_data, rename_samples
 from .mcmc import LazySamples
 
 
+def engine_draws(spec, posterior, n):
+    """Posterior sites -> the engine's coordinates, one species per handle: ``(fp_site, rate, draws_of)`` with ``draws_of(sp)`` the
+    (n, D) float32 matrix [beta, alpha, (phi), (log sds), (effects)] of species ``sp`` (the layout fit._assemble reads back), ``fp_site``
+    the name of the sampled false-positive rate (or None) and ``rate`` its draws.  Shared by ``predict`` and
+    ``latent.conditional_occupancy``."""
+    beta = np.asarray(posterior["beta"], dtype=np.float32)    # (n, S, Ks+1)
+    alpha = np.asarray(posterior["alpha"], dtype=np.float32)  # (n, S, Ko+1)
+    rate = phi = None
+    fp_site = f"prob_fp_{spec.extras['fp_mode']}" if spec.model == "occu_fp" else None
+    if spec.model in ("occu_re", "occu_rn") and spec.extras.get("re_fp_mode") is not None:   # (random effects +) a false-positive rate: [beta, alpha, phi, log sds, effects]
+        fp_site = f"prob_fp_{spec.extras['re_fp_mode']}"
+    if fp_site is not None:
+        rate = np.clip(np.asarray(posterior[fp_site], dtype=np.float64).reshape(n), 1e-300, 1 - 1e-16)
+        phi = np.log(rate / (1.0 - rate)).astype(np.float32)[:, None]   # the engine's coordinate: logit(rate)
+    if spec.model == "occu_cop" and spec.extras["fp_mode"] is not None:
+        fp_site = f"rate_fp_{spec.extras['fp_mode']}"
+        rate = np.maximum(np.asarray(posterior[fp_site], dtype=np.float64).reshape(n), 1e-300)
+        phi = np.log(rate).astype(np.float32)[:, None]                  # the engine's coordinate: log(rate)
+
+    def re_block(sp):
+        """The random-effects coordinates of species ``sp`` in the engine's one-species layout (see fit._assemble)."""
+        if spec.model != "occu_re" and not (spec.model in ("occu_rn", "nmixture", "occu_cop") and "site_random_effects" in spec.extras):
+            return None
+        cols = []
+        if spec.extras["site_random_effects"]:
+            cols.append(np.log(np.maximum(np.asarray(posterior["site_re_sd"], dtype=np.float64).reshape(n, 1), 1e-300)))
+        if spec.extras["obs_random_effects"]:
+            cols.append(np.log(np.maximum(np.asarray(posterior["obs_re_sd"], dtype=np.float64).reshape(n, 1), 1e-300)))
+        if spec.extras["site_random_effects"]:   # (n, N, species)
+            first = "site_re_abu" if spec.model in ("occu_rn", "nmixture") else "site_re_occ"   # (occu_rn.py:172-176, nmixture.py:166-169)
+            cols += [np.asarray(posterior[first])[..., sp].reshape(n, -1), np.asarray(posterior["site_re_det"])[..., sp].reshape(n, -1)]
+        if spec.extras["obs_random_effects"]:   # (n, J, T, N, species) -> [N][T][J]
+            cols.append(np.asarray(posterior["obs_re"])[..., sp].transpose(0, 3, 2, 1).reshape(n, -1))
+        return np.concatenate(cols, axis=1).astype(np.float32) if cols else None   # (occu_rn with a false-positive rate and no effects)
+
+    def draws_of(sp):
+        rb = re_block(sp)
+        return np.concatenate([beta[:, sp, :], alpha[:, sp, :]] + ([phi] if fp_site else []) + ([rb] if rb is not None else []), axis=1)
+
+    return fp_site, rate, draws_of
+
+
 def predict(
     model_fn: Callable,
     mcmc,
@@ -97,32 +139,7 @@ def predict(
     from ..engine import OccuDataset
     from .fit import engine_options
 
-    fp_site = f"prob_fp_{spec.extras['fp_mode']}" if spec.model == "occu_fp" else None
-    if spec.model in ("occu_re", "occu_rn") and spec.extras.get("re_fp_mode") is not None:   # (random effects +) a false-positive rate: [beta, alpha, phi, log sds, effects]
-        fp_site = f"prob_fp_{spec.extras['re_fp_mode']}"
-    if fp_site is not None:
-        rate = np.clip(np.asarray(posterior[fp_site], dtype=np.float64).reshape(n), 1e-300, 1 - 1e-16)
-        phi = np.log(rate / (1.0 - rate)).astype(np.float32)[:, None]   # the engine's coordinate: logit(rate)
-    if spec.model == "occu_cop" and spec.extras["fp_mode"] is not None:
-        fp_site = f"rate_fp_{spec.extras['fp_mode']}"
-        rate = np.maximum(np.asarray(posterior[fp_site], dtype=np.float64).reshape(n), 1e-300)
-        phi = np.log(rate).astype(np.float32)[:, None]                  # the engine's coordinate: log(rate)
-
-    def re_block(sp):
-        """The random-effects coordinates of species ``sp`` in the engine's one-species layout (see fit._assemble)."""
-        if spec.model != "occu_re" and not (spec.model in ("occu_rn", "nmixture", "occu_cop") and "site_random_effects" in spec.extras):
-            return None
-        cols = []
-        if spec.extras["site_random_effects"]:
-            cols.append(np.log(np.maximum(np.asarray(posterior["site_re_sd"], dtype=np.float64).reshape(n, 1), 1e-300)))
-        if spec.extras["obs_random_effects"]:
-            cols.append(np.log(np.maximum(np.asarray(posterior["obs_re_sd"], dtype=np.float64).reshape(n, 1), 1e-300)))
-        if spec.extras["site_random_effects"]:   # (n, N, species)
-            first = "site_re_abu" if spec.model in ("occu_rn", "nmixture") else "site_re_occ"   # (occu_rn.py:172-176, nmixture.py:166-169)
-            cols += [np.asarray(posterior[first])[..., sp].reshape(n, -1), np.asarray(posterior["site_re_det"])[..., sp].reshape(n, -1)]
-        if spec.extras["obs_random_effects"]:   # (n, J, T, N, species) -> [N][T][J]
-            cols.append(np.asarray(posterior["obs_re"])[..., sp].transpose(0, 3, 2, 1).reshape(n, -1))
-        return np.concatenate(cols, axis=1).astype(np.float32) if cols else None   # (occu_rn with a false-positive rate and no effects)
+    fp_site, rate, draws_of = engine_draws(spec, posterior, n)
 
     if spec.model == "occu_cs":   # sites psi, z, f, s (occu_cs.py:196-232); mu / sigma travel in the engine's coordinates
         from ..engine import OccuDataset
@@ -158,8 +175,7 @@ def predict(
         for sp in range(n_species):
             ds = OccuDataset(spec.site_covs, spec.obs_covs, spec.obs[sp:sp + 1], spec.prior_beta, spec.prior_alpha,
                              device=device, model=spec.model, **engine_options(spec))
-            rb = re_block(sp)
-            draws = np.concatenate([beta[:, sp, :], alpha[:, sp, :]] + ([phi] if fp_site else []) + ([rb] if rb is not None else []), axis=1)
+            draws = draws_of(sp)
             first.append(ds.deterministic(draws, psi=True, prob_detection=False)[0])
             lat, yy = ds.predictive(draws, seed=(int(random_seed) + (sp << 32)) & (2 ** 64 - 1))
             latent.append(lat)

@@ -366,6 +366,19 @@ int bl_predict_counts(bl_dataset *ds, int n_draws, const float *draws, uint64_t 
 int bl_predict_scores(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, uint8_t *latent, uint8_t *f, float *s);
 
 /*
+ * Conditional occupancy -- BUILDER-DEFINED, NO REFERENCE COUNTERPART (biolith/utils/predict.py withholds the observations, so its z
+ * is drawn from the prior).  Per posterior draw and (period, site), with the site-period's unmasked observations `obs`:
+ *   A = log psi + log p(obs | z = 1),   B = log(1 - psi) + log p(obs | z = 0)         (the terms, clamps and masks of bl_logp_grad)
+ *   log_lik [n_draws][T][N] = logaddexp(A, B) = log(psi p(obs | 1) + (1 - psi) p(obs | 0)):   sum over cells = the likelihood part of -U
+ *   z_prob  [n_draws][T][N] = exp(A - log_lik) = P(z = 1 | obs, theta)
+ *   z       [n_draws][T][N] ~ Bernoulli(z_prob), a function of (seed, draw, period, site) only (bl_predict's generator)
+ * A cell with no unmasked observation has log_lik = 0 exactly and z_prob = psi.  Host memory, NULL = skip.  draws [n_draws][D] float32 as
+ * for bl_predict.  Serves one-species handles of bl_dataset_create, _fp, _re, _re_fp and _comb (its three blocks; the scores through the
+ * per-period count / mean / squared-deviation rows); every other handle: BL_ERR_UNSUPPORTED, the message names the model.
+ */
+int bl_site_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *z_prob, uint8_t *z);
+
+/*
  * Multi-GPU: chain-parallel sampling and the gather of the draws.
  *
  * The reference's only multi-device strategy is chain_method="parallel" (biolith/utils/fit.py:109-113: one chain per
