@@ -114,3 +114,33 @@ def rename_samples(samples, site_covs_names=None, obs_covs_names: Optional[List[
             for i, name in enumerate(names):
                 samples[f"{prefix}{name}"] = block[..., i]
     return samples
+
+
+def engine_options(spec) -> dict:
+    """Model options of an ``OccuSpec`` as ``OccuDataset`` keyword arguments."""
+    ex = spec.extras
+    if spec.model == "occu_comb":   # (its observations are per species: species_dataset adds them)
+        return {k: ex[k] for k in ("ARU_obs_covs", "prior_fc", "prior_fu", "prior_mu", "prior_sigma")}
+    opts = dict(max_abundance=ex.get("max_abundance", 100))
+    if spec.model == "occu_fp":
+        opts.update(fp_mode=ex["fp_mode"], prior_fp=ex["prior_fp"])
+    if spec.model == "occu_cop":
+        opts.update(fp_mode=ex["fp_mode"], session_duration=ex["session_duration"], prior_fp_rate=ex.get("prior_fp_rate", 1.0))
+    if "site_random_effects" in ex:   # occu_re, and occu_rn / nmixture / occu_cop on the random-effects kernels
+        opts.update({k: ex[k] for k in ("site_random_effects", "obs_random_effects", "prior_site_re_sd", "prior_obs_re_sd")})
+        if ex.get("re_fp_mode") is not None:
+            opts.update(re_fp_mode=ex["re_fp_mode"], prior_fp=ex["prior_fp"])
+    if spec.model == "occu_cs":
+        opts.update(prior_mu=ex["prior_mu"], prior_sigma=ex["prior_sigma"])
+    return opts
+
+
+def species_dataset(spec, sp, device, joint=False):
+    """The device dataset of species ``sp`` of an ``OccuSpec`` (``joint``: of all its species in one handle)."""
+    from ..engine import OccuDataset
+
+    one = slice(None) if joint else slice(sp, sp + 1)
+    opts = engine_options(spec)
+    if spec.model == "occu_comb":
+        opts.update(ARU_obs=spec.extras["ARU_obs"][one], scores_obs=spec.extras["scores_obs"][one])
+    return OccuDataset(spec.site_covs, spec.obs_covs, spec.obs[one], spec.prior_beta, spec.prior_alpha, device=device, model=spec.model, **opts)

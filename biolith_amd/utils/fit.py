@@ -7,6 +7,7 @@ calls ``mcmc.run`` (fit.py:92-130), this lowers the model onto the C-ABI in
 """
 from __future__ import annotations
 
+import copy
 import os
 import time
 from collections import namedtuple
@@ -14,8 +15,11 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from .data import prepare_data, rename_samples
+from .data import prepare_data, rename_samples, species_dataset
+from .init import as_strategy, comb_initial_positions, initial_positions
+from .layout import layout_for, sites_from_draws, species_block
 from .mcmc import HipMCMC
+from .misc import time_limit
 
 FitResult = namedtuple("FitResult", ["samples", "mcmc"])
 
@@ -67,8 +71,6 @@ def fit(
         raise NotImplementedError(f"kernel={kernel!r}: the HIP engine implements NUTS only (fit.py:92-104)")
     if kernel != "nuts":
         raise KeyError(kernel)
-    from .init import as_strategy, initial_positions
-
     strategy = as_strategy(init_strategy)   # None = init_to_uniform (fit.py:93); NotImplementedError for anything unknown
     device = int(kwargs.pop("device", 0))
     devices = kwargs.pop("devices", None)
@@ -87,7 +89,6 @@ def fit(
     spec = model_fn(**valid, **kwargs)
 
     from ..distributed import shard_chains
-    from ..engine import OccuDataset
 
     # The "species" plate (occu.py:182-186) carries its own beta/alpha per species over shared covariates,
     # so the joint posterior is a product over species: each species gets its own device dataset and
@@ -114,18 +115,18 @@ def fit(
                 count, first = shard_chains(num_chains, world, r)
                 if count == 0:
                     continue
-                if spec.model == "occu_comb":
-                    jobs.append(_comb_job(spec, sp, dev, strategy, dict(num_warmup=num_warmup, num_samples=num_samples, num_chains=count,
-                                                                         seed=random_seed, chain_offset=chain_offset + sp * num_chains + first)))
-                    continue
-                ds = OccuDataset(spec.site_covs, spec.obs_covs, spec.obs if joint else spec.obs[sp:sp + 1], spec.prior_beta, spec.prior_alpha,
-                                 device=dev, model=spec.model, **engine_options(spec))
+                ds = species_dataset(spec, sp, dev, joint)
+                layout = _layout_of(spec, ds, n_species if joint else 1)
+                assert layout.D == ds.D, f"{spec.model}: the layout has {layout.D} coordinates, the engine's handle {ds.D}"
                 kw = dict(num_warmup=num_warmup, num_samples=num_samples, num_chains=count,
                           seed=random_seed, chain_offset=chain_offset + sp * num_chains + first)
-                nsp_here = n_species if joint else 1
-                init = initial_positions(strategy, D=ds.D, Ks=ds.Ks, Ko=ds.Ko, n_species=nsp_here, plain=ds.D == nsp_here * (ds.Ks + ds.Ko + 2) and spec.model != "occu_dyn", blocks_first=spec.model != "occu_dyn",
-                                         prior_beta=spec.prior_beta, prior_alpha=spec.prior_alpha, num_chains=count,
-                                         first_chain=kw["chain_offset"], seed=random_seed, species=sp)
+                if spec.model == "occu_comb":
+                    init = comb_initial_positions(strategy, Ks=ds.Ks, Kpc=ds.Ko, Karu=ds.Ka, num_chains=count, first_chain=kw["chain_offset"],
+                                                  seed=random_seed, species=sp)
+                else:
+                    init = initial_positions(strategy, D=ds.D, Ks=ds.Ks, Ko=ds.Ko, n_species=layout.S, plain=layout.plain, blocks_first=spec.model != "occu_dyn",
+                                             prior_beta=spec.prior_beta, prior_alpha=spec.prior_alpha, num_chains=count,
+                                             first_chain=kw["chain_offset"], seed=random_seed, species=sp)
                 if init is not None:
                     kw["init_theta"] = init
                 jobs.append((sp, ds, kw))
@@ -238,12 +239,7 @@ def fit(
             return run_retrying()
 
     try:
-        if timeout is not None:
-            from .misc import time_limit
-
-            with time_limit(timeout):
-                results = run_with_fallback()
-        else:
+        with time_limit(timeout):
             results = run_with_fallback()
     finally:
         for c in comms:
@@ -261,30 +257,13 @@ def fit(
     if joint:
         # one launch holds every species: cut its draws into the per-species blocks the site assembly works on (deterministic
         # sites come from one plain handle per species; the shared false-positive coordinate rides along with every block)
-        import copy
-
         ds_joint, joint_result = per_species[0]
-        Dsp = ds_joint.Ks + ds_joint.Ko + 2
+        joint_layout = _layout_of(spec, ds_joint, n_species)
         per_species = []
-        jd = joint_result.draws
         for sp in range(n_species):
             part = copy.copy(joint_result)
-            if spec.model == "occu_re":
-                # [species' beta, alpha | log sds | site_re_occ [S][N] | site_re_det [S][N] | obs_re [S][N][T][J]] -> the one-species layout
-                N, V = ds_joint.N, ds_joint.T * ds_joint.J
-                nsd = int(ds_joint.site_re) + int(ds_joint.obs_re)
-                at = n_species * Dsp + nsd
-                blocks = [jd[:, :, sp * Dsp:(sp + 1) * Dsp], jd[:, :, n_species * Dsp: at]]
-                if ds_joint.site_re:
-                    blocks += [jd[:, :, at + sp * N: at + (sp + 1) * N], jd[:, :, at + (n_species + sp) * N: at + (n_species + sp + 1) * N]]
-                    at += 2 * n_species * N
-                if ds_joint.obs_re:
-                    blocks.append(jd[:, :, at + sp * N * V: at + (sp + 1) * N * V])
-                part.draws = np.ascontiguousarray(np.concatenate(blocks, axis=2))
-            else:
-                part.draws = np.ascontiguousarray(np.concatenate([jd[:, :, sp * Dsp:(sp + 1) * Dsp], jd[:, :, n_species * Dsp:]], axis=2))
-            per_species.append((OccuDataset(spec.site_covs, spec.obs_covs, spec.obs[sp:sp + 1], spec.prior_beta, spec.prior_alpha,
-                                            device=devices[0], model=spec.model, **engine_options(spec)), part))
+            part.draws = species_block(joint_layout, joint_result.draws, sp)
+            per_species.append((species_dataset(spec, sp, devices[0]), part))
     if spec.model == "occu_dyn":
         mcmc = _assemble_dyn(per_species[0], spec, num_warmup)
         samples = rename_samples(mcmc.get_samples(), site_names, obs_names)
@@ -301,62 +280,9 @@ def fit(
     return FitResult(samples, mcmc)
 
 
-def engine_options(spec) -> dict:
-    """Model options of an ``OccuSpec`` as ``OccuDataset`` keyword arguments."""
-    opts = dict(max_abundance=spec.extras.get("max_abundance", 100))
-    if spec.model == "occu_fp":
-        opts.update(fp_mode=spec.extras["fp_mode"], prior_fp=spec.extras["prior_fp"])
-    if spec.model == "occu_cop":
-        opts.update(fp_mode=spec.extras["fp_mode"], session_duration=spec.extras["session_duration"],
-                    prior_fp_rate=spec.extras.get("prior_fp_rate", 1.0))
-    if spec.model == "occu_re":
-        opts.update({k: spec.extras[k] for k in ("site_random_effects", "obs_random_effects", "prior_site_re_sd", "prior_obs_re_sd")})
-        if spec.extras.get("re_fp_mode") is not None:
-            opts.update(re_fp_mode=spec.extras["re_fp_mode"], prior_fp=spec.extras["prior_fp"])
-    if spec.model in ("nmixture", "occu_rn", "occu_cop") and "site_random_effects" in spec.extras:
-        opts.update({k: spec.extras[k] for k in ("site_random_effects", "obs_random_effects", "prior_site_re_sd", "prior_obs_re_sd")})
-        if spec.extras.get("re_fp_mode") is not None:   # occu_rn with a false-positive rate
-            opts.update(re_fp_mode=spec.extras["re_fp_mode"], prior_fp=spec.extras["prior_fp"])
-    if spec.model == "occu_cs":
-        opts.update(prior_mu=spec.extras["prior_mu"], prior_sigma=spec.extras["prior_sigma"])
-    return opts
-
-
-def comb_dataset(spec, sp, device):
-    """The device dataset of species ``sp`` of an occu_comb ``OccuSpec`` (fit's jobs and ``latent.conditional_occupancy``)."""
-    from ..engine import OccuDataset
-
-    ex = spec.extras
-    return OccuDataset(spec.site_covs, spec.obs_covs, spec.obs[sp:sp + 1], spec.prior_beta, spec.prior_alpha, device=device, model="occu_comb",
-                       ARU_obs_covs=ex["ARU_obs_covs"], ARU_obs=ex["ARU_obs"][sp:sp + 1], scores_obs=ex["scores_obs"][sp:sp + 1],
-                       prior_fc=ex["prior_fc"], prior_fu=ex["prior_fu"], prior_mu=ex["prior_mu"], prior_sigma=ex["prior_sigma"])
-
-
-def comb_engine_draws(posterior, sp):
-    """occu_comb: the posterior's sample sites of species ``sp`` back in the engine's coordinates, (n, D) float32 -- the inverse of
-    what ``_assemble_comb`` reads out of a draw: [beta | alpha_PC | alpha_ARU | logit fc | logit fu | mu0 | log(mu1 - mu0) | log sigma0 |
-    log sigma1]."""
-    g = lambda k: np.asarray(posterior[k], dtype=np.float64)[:, sp]
-    n = g("beta").shape[0]
-    col = lambda k: g(k).reshape(n, 1)
-    logit = lambda f: np.log(np.clip(f, 1e-300, 1 - 1e-16) / (1.0 - np.clip(f, 1e-300, 1 - 1e-16)))
-    return np.concatenate([g("beta"), g("alpha_PC"), g("alpha_ARU"), logit(col("ARU_prob_fp_constant")), logit(col("ARU_fp_unoccupied")),
-                           col("mu0"), np.log(np.maximum(col("mu1") - col("mu0"), 1e-300)), np.log(col("sigma0")), np.log(col("sigma1"))],
-                          axis=1).astype(np.float32)
-
-
-def _comb_job(spec, sp, device, strategy, kw):
-    """occu_comb: species ``sp`` as a launch of its own (nothing is shared across the species plate, occu_comb.py:224-248, so the
-    joint posterior factorises).  theta = [beta | alpha_PC | alpha_ARU | logit fc | logit fu | mu0 | log(mu1 - mu0) | log sigma0 |
-    log sigma1]."""
-    from .init import comb_initial_positions
-
-    ds = comb_dataset(spec, sp, device)
-    init = comb_initial_positions(strategy, Ks=ds.Ks, Kpc=ds.Ko, Karu=ds.Ka, num_chains=kw["num_chains"], first_chain=kw["chain_offset"],
-                                  seed=kw["seed"], species=sp)
-    if init is not None:
-        kw["init_theta"] = init
-    return sp, ds, kw
+def _layout_of(spec, ds, species_in_handle=1):
+    """The layout of the handle ``ds`` of ``spec``'s model."""
+    return layout_for(spec, N=ds.N, T=ds.T, J=ds.J, Ks=ds.Ks, Ko=ds.Ko, Ka=getattr(ds, "Ka", None), species_in_handle=species_in_handle)
 
 
 def _assemble_comb(per_species, spec, num_warmup) -> HipMCMC:
@@ -364,17 +290,7 @@ def _assemble_comb(per_species, spec, num_warmup) -> HipMCMC:
     psi and the detection probabilities are formed here from the draws (the engine's bl_deterministic does not serve this model)."""
     ds0, res0 = per_species[0]
     C, S, D = res0.draws.shape
-    Ks, Kp, Ka = ds0.Ks, ds0.Ko, ds0.Ka
-    nsp = len(per_species)
-    dr = np.stack([r.draws for _, r in per_species], axis=2)                      # (C, S, nsp, D)
-    o = Ks + Kp + Ka + 3
-    e = dr[..., o:].astype(np.float64)
-    latent = dict(beta=dr[..., :Ks + 1], alpha_PC=dr[..., Ks + 1: Ks + Kp + 2], alpha_ARU=dr[..., Ks + Kp + 2: o])
-    latent["ARU_prob_fp_constant"] = (1.0 / (1.0 + np.exp(-e[..., 0]))).astype(np.float32)
-    latent["ARU_fp_unoccupied"] = (1.0 / (1.0 + np.exp(-e[..., 1]))).astype(np.float32)
-    latent["mu0"] = e[..., 2].astype(np.float32)
-    latent["mu1"] = (e[..., 2] + np.exp(e[..., 3])).astype(np.float32)
-    latent["sigma0"], latent["sigma1"] = np.exp(e[..., 4]).astype(np.float32), np.exp(e[..., 5]).astype(np.float32)
+    latent = sites_from_draws(_layout_of(spec, ds0), [r.draws for _, r in per_species])
     T = spec.obs_covs.shape[1]
 
     def sigmoid(lin):
@@ -405,19 +321,7 @@ def _assemble_comb(per_species, spec, num_warmup) -> HipMCMC:
         z1 = (1.0 - (1.0 - p) * (1.0 - fc)).astype(np.float32)
         return np.stack([z0, z1], axis=2)
 
-    import copy
-
-    res = copy.copy(res0)
-    if nsp > 1:
-        res.diverging = np.logical_or.reduce([r.diverging for _, r in per_species])
-        res.num_steps = np.sum([r.num_steps for _, r in per_species], axis=0)
-        res.accept_prob = np.mean([r.accept_prob for _, r in per_species], axis=0)
-        res.potential_energy = np.sum([r.potential_energy for _, r in per_species], axis=0)
-        res.n_leapfrog = np.sum([r.n_leapfrog for _, r in per_species], axis=0)
-        res.kernel_ms = float(np.sum([r.kernel_ms for _, r in per_species]))
-        res.inv_mass = np.concatenate([r.inv_mass for _, r in per_species], axis=1)
-        res.draws = np.concatenate([r.draws for _, r in per_species], axis=2)
-    return HipMCMC(res, latent=latent,
+    return HipMCMC(_merge_species([r for _, r in per_species]), latent=latent,
                    deterministic=dict(psi=_memo(psi), PC_prob_detection=_memo(detection("alpha_PC", spec.obs_covs)),
                                       ARU_prob_detection=_memo(detection("alpha_ARU", spec.extras["ARU_obs_covs"])),
                                       ARU_prob_detection_fp=_memo(prob_detection_fp)),
@@ -434,12 +338,26 @@ def _memo(fn):   # a site is computed once, on its first access
     return get
 
 
+def _merge_species(parts):
+    """One NutsResult per species (samplers of their own) -> one result object for the mcmc shim: per-draw fields combined over
+    species, draws and inverse mass concatenated on the coordinate axis."""
+    res = copy.copy(parts[0])
+    if len(parts) > 1:
+        res.diverging = np.logical_or.reduce([r.diverging for r in parts])
+        res.num_steps = np.sum([r.num_steps for r in parts], axis=0)
+        res.accept_prob = np.mean([r.accept_prob for r in parts], axis=0)
+        res.potential_energy = np.sum([r.potential_energy for r in parts], axis=0)
+        res.n_leapfrog = np.sum([r.n_leapfrog for r in parts], axis=0)
+        res.kernel_ms = float(np.sum([r.kernel_ms for r in parts]))
+        res.inv_mass = np.concatenate([r.inv_mass for r in parts], axis=1)
+        res.draws = np.concatenate([r.draws for r in parts], axis=2)
+    return res
+
+
 def _concat_chains(parts):
     """Shards of one species' chains (one NutsResult per device) -> one NutsResult, chain axis first."""
     if len(parts) == 1:
         return parts[0]
-    import copy
-
     res = copy.copy(parts[0])
     for name in ("draws", "diverging", "num_steps", "accept_prob", "potential_energy", "step_size", "inv_mass", "n_leapfrog"):
         setattr(res, name, np.concatenate([getattr(r, name) for r in parts], axis=0))
@@ -453,9 +371,7 @@ def _assemble_dyn(ds_res, spec, num_warmup) -> HipMCMC:
     species plate last as everywhere (one species); psi / gamma / epsilon per site are formed lazily on the host."""
     ds0, res = ds_res
     C, S, D = res.draws.shape
-    Ks, Ko, B = ds0.Ks, ds0.Ko, ds0.Ks + 1
-    blocks = [res.draws[:, :, b * B:(b + 1) * B][:, :, None, :] for b in range(3)]
-    latent = dict(beta=blocks[0], beta_col=blocks[1], beta_ext=blocks[2], alpha=res.draws[:, :, 3 * B:][:, :, None, :])
+    latent = sites_from_draws(_layout_of(spec, ds0), [res.draws])
     X = np.nan_to_num(np.asarray(spec.site_covs, dtype=np.float32))
 
     def site(block):
@@ -465,7 +381,7 @@ def _assemble_dyn(ds_res, spec, num_warmup) -> HipMCMC:
             return (1.0 / (1.0 + np.exp(-eta)))[..., None].astype(np.float32)      # (C, S, N, species)
         return get
 
-    return HipMCMC(res, latent=latent, deterministic=dict(psi=site(blocks[0]), gamma=site(blocks[1]), epsilon=site(blocks[2])),
+    return HipMCMC(res, latent=latent, deterministic=dict(psi=site(latent["beta"]), gamma=site(latent["beta_col"]), epsilon=site(latent["beta_ext"])),
                    num_warmup=num_warmup, spec_shape=spec.shape)
 
 
@@ -473,60 +389,11 @@ def _assemble(per_species, spec, num_warmup, joint_result=None) -> HipMCMC:
     """Draws (C, S, D) per species -> the sample sites the reference's model emits (occu.py:185-228)."""
     ds0, res0 = per_species[0]
     C, S, D = res0.draws.shape
-    Ks, Ko = ds0.Ks, ds0.Ko
     nsp = len(per_species)
-    # plate "species" is the last axis of every site (occu.py:182, dim=-1)
-    beta = np.stack([r.draws[:, :, : Ks + 1] for _, r in per_species], axis=2)     # (C, S, nsp, Ks+1)
-    alpha = np.stack([r.draws[:, :, Ks + 1: Ks + Ko + 2] for _, r in per_species], axis=2)  # (C, S, nsp, Ko+1)
-    latent = dict(beta=beta, alpha=alpha)
-    if spec.model == "occu_fp":
-        # the engine samples phi = logit(rate); the model's site is the rate itself, shape (C, S) (occu.py:146-157)
-        phi = res0.draws[:, :, Ks + Ko + 2].astype(np.float64)
-        latent[f"prob_fp_{spec.extras['fp_mode']}"] = (1.0 / (1.0 + np.exp(-phi))).astype(np.float32)
-    if spec.model == "occu_cop" and spec.extras["fp_mode"] is not None:
-        # phi = log(rate); the model's site is the rate (occu_cop.py:158-170)
-        latent[f"rate_fp_{spec.extras['fp_mode']}"] = np.exp(res0.draws[:, :, Ks + Ko + 2].astype(np.float64)).astype(np.float32)
-    if spec.model == "occu_cs":
-        # theta = [beta, alpha, mu0, log(mu1 - mu0), log sigma0, log sigma1]; the model's sites are mu0, mu1, sigma0, sigma1 (occu_cs.py:143-152)
-        e = res0.draws[:, :, Ks + Ko + 2:].astype(np.float64)
-        latent["mu0"] = e[..., 0].astype(np.float32)
-        latent["mu1"] = (e[..., 0] + np.exp(e[..., 1])).astype(np.float32)
-        latent["sigma0"], latent["sigma1"] = np.exp(e[..., 2]).astype(np.float32), np.exp(e[..., 3]).astype(np.float32)
-    if spec.model == "occu_re" or (spec.model in ("nmixture", "occu_rn", "occu_cop") and "site_random_effects" in spec.extras):
-        # theta = [beta, alpha, (log site_re_sd), (log obs_re_sd), (site_re_occ[N], site_re_det[N]), (obs_re[N][T][J])]; the
-        # model's sites are the sds themselves, the effects with the species plate last (occu.py:170-173, 191-196, 215-218)
-        N, T, J = ds0.N, ds0.T, ds0.J
-        at = Ks + Ko + 2
-        if spec.model == "occu_cop" and spec.extras["fp_mode"] is not None:   # [beta, alpha, phi = log(rate), log sds, effects]: the rate was read above
-            at += 1
-        if spec.extras.get("re_fp_mode") is not None:   # [beta, alpha, phi = logit(rate), log sds, effects]
-            phi = res0.draws[:, :, at].astype(np.float64)
-            latent[f"prob_fp_{spec.extras['re_fp_mode']}"] = (1.0 / (1.0 + np.exp(-phi))).astype(np.float32)
-            at += 1
-        if spec.extras["site_random_effects"]:
-            latent["site_re_sd"] = np.exp(res0.draws[:, :, at].astype(np.float64)).astype(np.float32)
-            at += 1
-        if spec.extras["obs_random_effects"]:
-            latent["obs_re_sd"] = np.exp(res0.draws[:, :, at].astype(np.float64)).astype(np.float32)
-            at += 1
-        if spec.extras["site_random_effects"]:
-            # (the abundance models name the first one after their predictor: nmixture.py:166-169, occu_rn.py:172-176)
-            latent["site_re_abu" if spec.model in ("nmixture", "occu_rn") else "site_re_occ"] = np.stack([r.draws[:, :, at: at + N] for _, r in per_species], axis=-1)   # (C, S, N, nsp)
-            latent["site_re_det"] = np.stack([r.draws[:, :, at + N: at + 2 * N] for _, r in per_species], axis=-1)
-            at += 2 * N
-        if spec.extras["obs_random_effects"]:
-            e = np.stack([r.draws[:, :, at: at + N * T * J].reshape(C, S, N, T, J) for _, r in per_species], axis=-1)
-            latent["obs_re"] = np.ascontiguousarray(e.transpose(0, 1, 4, 3, 2, 5))                                   # (C, S, J, T, N, nsp)
-    def memo(fn):   # a site is computed once, on its first access
-        box = []
+    # plate "species" is the last axis of every site (occu.py:182, dim=-1); the sampled sites are the rates and sds themselves
+    latent = sites_from_draws(_layout_of(spec, ds0), [r.draws for _, r in per_species])
 
-        def get():
-            if not box:
-                box.append(fn())
-            return box[0]
-        return get
-
-    @memo
+    @_memo
     def psi():
         # (as the reference's samples stay on the device until they are looked at, so does this site: 160 MB over PCIe at the
         # headline size would otherwise be a sixth of fit()'s wall time)
@@ -537,13 +404,13 @@ def _assemble(per_species, spec, num_warmup, joint_result=None) -> HipMCMC:
         out = parts[0][..., None] if nsp == 1 else np.stack(parts, axis=-1)
         return out.reshape(C, S, ds0.T, ds0.N, nsp)
 
-    @memo
+    @_memo
     def prob_detection():
         parts = [d.deterministic(r.draws.reshape(C * S, D), psi=False, prob_detection=True)[1] for d, r in per_species]
         pd = parts[0][..., None] if nsp == 1 else np.stack(parts, axis=-1)
         return pd.reshape(C, S, ds0.J, ds0.T, ds0.N, nsp)
 
-    @memo
+    @_memo
     def prob_detection_fp():
         # occu.py:229-235: 1 - (1 - z p)(1 - f_c)(1 - (1 - z) f_u) depends on the ENUMERATED z, so under numpyro's parallel
         # enumeration (occu.py:208-210) the recorded value carries z's enumeration axis in front of the plates
@@ -559,22 +426,8 @@ def _assemble(per_species, spec, num_warmup, joint_result=None) -> HipMCMC:
         z1 = (1.0 - (1.0 - pd) * (1.0 - f_c)).astype(np.float32)
         return np.stack([z0, z1], axis=2)
 
-    # one result object for the mcmc shim: extras concatenated over species along the chain axis
-    import copy
-
-    res = copy.copy(res0)
-    if joint_result is not None:
-        res = copy.copy(joint_result)    # one chain over all species: its per-draw fields are the sampler's own
-    elif nsp > 1:
-        res.diverging = np.logical_or.reduce([r.diverging for _, r in per_species])
-        res.num_steps = np.sum([r.num_steps for _, r in per_species], axis=0)
-        res.accept_prob = np.mean([r.accept_prob for _, r in per_species], axis=0)
-        res.potential_energy = np.sum([r.potential_energy for _, r in per_species], axis=0)
-        res.n_leapfrog = np.sum([r.n_leapfrog for _, r in per_species], axis=0)
-        res.kernel_ms = float(np.sum([r.kernel_ms for _, r in per_species]))
-        res.inv_mass = np.concatenate([r.inv_mass for _, r in per_species], axis=1)
-    if joint_result is None:
-        res.draws = np.concatenate([r.draws for _, r in per_species], axis=2) if nsp > 1 else res0.draws
+    # (one chain over all species: its per-draw fields are the sampler's own)
+    res = copy.copy(joint_result) if joint_result is not None else _merge_species([r for _, r in per_species])
     # occu emits "psi" (occu.py:207); occu_rn emits "abundance" = exp(linear predictor) (occu_rn.py:192)
     first = "abundance" if spec.model in ("occu_rn", "nmixture") else "psi"
     # occu_cop's replicate-level site is the detection RATE exp(linear predictor) (occu_cop.py:236-243)

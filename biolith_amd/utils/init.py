@@ -17,9 +17,12 @@ arguments, so a reference-style call keeps working.  Draw-level equality with Nu
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Any, Dict, Optional
 
 import numpy as np
+
+from .layout import layout_for
 
 
 @dataclass(frozen=True)
@@ -79,111 +82,90 @@ def _prior_draws(rng, prior, shape):
     return rng.normal(loc, scale, size=shape)
 
 
-def initial_positions(strategy: Optional[InitStrategy], *, D: int, Ks: int, Ko: int, n_species: int, plain: bool, blocks_first: bool = True, prior_beta, prior_alpha,
-                      num_chains: int, first_chain: int, seed: int, species: int = 0):
-    """Start positions ``(num_chains, D)`` float64 for one launch, or None when the kernel's own draw applies (``init_to_uniform`` at
-    radius 2).  theta = [species 0: beta (Ks + 1), alpha (Ko + 1) | species 1: ... | further unconstrained coordinates]; ``n_species``
-    species blocks lie in THIS launch's theta (one unless the species are sampled jointly), the launch's first species is ``species``;
-    ``plain``: theta holds nothing but those coefficient blocks; ``blocks_first``: it starts with them (all models but the dynamic one).  Chain c of the fit gets its own generator (seed, c): what a chain starts
-    from does not depend on how the chains are dealt to launches."""
+_COEFFICIENTS_ONLY = ("built for models whose coordinates are all regression coefficients "
+                      "(no false-positive rate, random effects or score parameters); use init_to_uniform / _feasible / _value")
+
+
+def _coordinates(block, v, sp, theta):
+    """``init_to_value``: the value ``v`` given for ``block``'s site -> species ``sp``'s coordinates (``theta``: the chain's start so far)."""
+    if block.width > 1 or len(block.shape) > 1:
+        row = v if v.ndim == 1 else v[sp]   # (n_species, K + 1), the reference's site shape, or one row for all
+        if row.shape != (block.width,):
+            raise ValueError(f"init_to_value: {block.site} must have {block.width} coefficients per species, got shape {v.shape}")
+        return row
+    x = float(v.reshape(-1)[sp] if v.size > 1 else v.reshape(()))   # a scalar, or one value per species
+    if block.transform == "sigmoid":
+        if not 0.0 < x < 1.0:
+            raise ValueError(f"init_to_value: {block.site} must lie in (0, 1)")
+        return np.log(x) - np.log1p(-x)
+    if block.transform == "gap":
+        x -= theta[block.offset - 1]
+        if not x > 0.0:
+            raise ValueError(f"init_to_value: {block.site} must exceed mu0 (its prior is truncated below at mu0)")
+    elif block.transform == "exp" and not x > 0.0:
+        raise ValueError(f"init_to_value: {block.site} must be positive")
+    return x if block.transform == "identity" else np.log(x)
+
+
+def _start_positions(strategy, layout, *, D, priors, num_chains, first_chain, seed, species):
+    """Start positions ``(num_chains, D)`` float64 of one launch, or None when the kernel's own draw applies (``init_to_uniform`` at
+    radius 2).  ``layout`` names the blocks ``init_to_value`` may set (constrained values in, the engine's coordinates out);
+    ``priors``: site -> coefficient prior when theta is nothing but those sites (``init_to_mean`` / ``_median`` / ``_sample``), else
+    None.  Chain c of the fit gets its own generator (seed, c): what a chain starts from does not depend on how the chains are dealt
+    to launches."""
     if strategy is None or (strategy.kind == "uniform" and strategy.radius == 2.0):
         return None
-    Dsp = Ks + Ko + 2
+    vals = {k: np.asarray(v, dtype=np.float64) for k, v in strategy.values.items()}
+    unknown = set(vals) - {b.site for b in layout.blocks}
+    if unknown:
+        raise NotImplementedError(f"init_to_value: sites {sorted(unknown)} are not sampled sites of {layout.model}")
+    if strategy.kind in ("mean", "median", "sample") and priors is None:
+        raise NotImplementedError(f"init_to_{strategy.kind}: {_COEFFICIENTS_ONLY}")
+    radius = strategy.radius if strategy.kind == "uniform" else 2.0
     out = np.empty((num_chains, D), dtype=np.float64)
     for c in range(num_chains):
         rng = np.random.default_rng([int(seed) & 0x7FFFFFFF, first_chain + c, 0x1B1D])
         if strategy.kind == "feasible":
             out[c] = 0.0
             continue
-        radius = strategy.radius if strategy.kind == "uniform" else 2.0
         out[c] = rng.uniform(-radius, radius, size=D)
-        if strategy.kind == "uniform":
+        if strategy.kind in ("uniform", "value"):
+            for b, s in ((b, s) for b in layout.blocks if b.site in vals for s in range(layout.S)):
+                out[c, b.offset + s * b.stride: b.offset + s * b.stride + b.width] = _coordinates(b, vals[b.site], species + s, out[c])
             continue
-        if strategy.kind == "value":
-            vals = {k: np.asarray(v, dtype=np.float64) for k, v in strategy.values.items()}
-            unknown = set(vals) - {"beta", "alpha"}
-            if unknown:
-                raise NotImplementedError(f"init_to_value: sites {sorted(unknown)} are not coefficient sites of this engine (beta, alpha)")
-            if not blocks_first and vals:
-                raise NotImplementedError("init_to_value: not built for the dynamic model's coefficient layout")
-            for s in range(n_species):
-                for name, off, width in (("beta", 0, Ks + 1), ("alpha", Ks + 1, Ko + 1)):
-                    if name in vals:
-                        v = vals[name]
-                        row = v if v.ndim == 1 else v[species + s]   # (n_species, K + 1), the reference's site shape, or one row for all
-                        if row.shape != (width,):
-                            raise ValueError(f"init_to_value: {name} must have {width} coefficients per species, got shape {v.shape}")
-                        out[c, s * Dsp + off: s * Dsp + off + width] = row
-            continue
-        if not plain:
-            raise NotImplementedError(f"init_to_{strategy.kind}: built for models whose coordinates are all regression coefficients "
-                                      "(no false-positive rate, random effects or score parameters); use init_to_uniform / _feasible / _value")
         n = 1 if strategy.kind == "sample" else strategy.num_samples
-        for s in range(n_species):
-            for prior, off, width in ((prior_beta, 0, Ks + 1), (prior_alpha, Ks + 1, Ko + 1)):
-                if strategy.kind == "mean":
-                    col = np.full(width, float(prior[0]))
-                else:
-                    col = np.median(_prior_draws(rng, prior, (n, width)), axis=0)
-                out[c, s * Dsp + off: s * Dsp + off + width] = col
+        for s in range(layout.S):
+            for b in layout.blocks:
+                prior = priors[b.site]
+                col = np.full(b.width, float(prior[0])) if strategy.kind == "mean" else np.median(_prior_draws(rng, prior, (n, b.width)), axis=0)
+                out[c, b.offset + s * b.stride: b.offset + s * b.stride + b.width] = col
     return out
+
+
+def initial_positions(strategy: Optional[InitStrategy], *, D: int, Ks: int, Ko: int, n_species: int, plain: bool, blocks_first: bool = True, prior_beta, prior_alpha,
+                      num_chains: int, first_chain: int, seed: int, species: int = 0):
+    """Start positions for every model but occu_comb.  ``n_species`` species' coefficient blocks lie in THIS launch's theta of ``D``
+    coordinates (one unless the species are sampled jointly), the launch's first species is ``species``; ``plain``: theta holds nothing
+    but those coefficient blocks; ``blocks_first``: it starts with [beta, alpha] (all models but the dynamic one).  ``init_to_value``
+    sets ``beta`` / ``alpha`` only."""
+    if plain and not blocks_first:
+        raise ValueError("initial_positions: the dynamic model's theta is not plain [beta, alpha] (plain=True needs blocks_first=True)")
+    if strategy is not None and strategy.kind == "value":
+        unknown = set(strategy.values) - {"beta", "alpha"}
+        if unknown:
+            raise NotImplementedError(f"init_to_value: sites {sorted(unknown)} are not coefficient sites of this engine (beta, alpha)")
+        if not blocks_first and strategy.values:
+            raise NotImplementedError("init_to_value: not built for the dynamic model's coefficient layout")
+    coefficients = layout_for(SimpleNamespace(model="occu" if blocks_first else "occu_dyn", extras={}), N=0, T=0, J=0, Ks=Ks, Ko=Ko,
+                              species_in_handle=n_species)
+    return _start_positions(strategy, coefficients, D=D, priors=dict(beta=prior_beta, alpha=prior_alpha) if plain else None,
+                            num_chains=num_chains, first_chain=first_chain, seed=seed, species=species)
 
 
 def comb_initial_positions(strategy: Optional[InitStrategy], *, Ks: int, Kpc: int, Karu: int, num_chains: int, first_chain: int,
                            seed: int, species: int = 0):
-    """``initial_positions`` for occu_comb (one species per launch): theta = [beta | alpha_PC | alpha_ARU | logit fc | logit fu | mu0 |
-    log(mu1 - mu0) | log sigma0 | log sigma1].  ``init_to_value`` takes the reference's site names with constrained values
-    (``ARU_prob_fp_constant``, ``ARU_fp_unoccupied``, ``mu0``, ``mu1``, ``sigma0``, ``sigma1``: a scalar, or one value per species;
-    the coefficients as ``(n_species, K + 1)`` or one row); everything not named starts as ``init_to_uniform``."""
-    if strategy is None or (strategy.kind == "uniform" and strategy.radius == 2.0):
-        return None
-    if strategy.kind not in ("uniform", "feasible", "value"):
-        raise NotImplementedError(f"init_to_{strategy.kind}: built for models whose coordinates are all regression coefficients "
-                                  "(no false-positive rate, random effects or score parameters); use init_to_uniform / _feasible / _value")
-    o = Ks + Kpc + Karu + 3
-    D = o + 6
-    blocks = dict(beta=(0, Ks + 1), alpha_PC=(Ks + 1, Kpc + 1), alpha_ARU=(Ks + Kpc + 2, Karu + 1))
-    scalars = ("ARU_prob_fp_constant", "ARU_fp_unoccupied", "mu0", "mu1", "sigma0", "sigma1")
-    vals = {k: np.asarray(v, dtype=np.float64) for k, v in strategy.values.items()}
-    unknown = set(vals) - set(blocks) - set(scalars)
-    if unknown:
-        raise NotImplementedError(f"init_to_value: sites {sorted(unknown)} are not sampled sites of occu_comb")
-
-    def scalar(name):
-        v = vals[name]
-        return float(v.reshape(-1)[species] if v.size > 1 else v.reshape(()))
-
-    out = np.empty((num_chains, D), dtype=np.float64)
-    for c in range(num_chains):
-        rng = np.random.default_rng([int(seed) & 0x7FFFFFFF, first_chain + c, 0x1B1D])
-        if strategy.kind == "feasible":
-            out[c] = 0.0
-            continue
-        out[c] = rng.uniform(-strategy.radius if strategy.kind == "uniform" else -2.0, strategy.radius if strategy.kind == "uniform" else 2.0, size=D)
-        for name, (off, width) in blocks.items():
-            if name in vals:
-                v = vals[name]
-                row = v if v.ndim == 1 else v[species]
-                if row.shape != (width,):
-                    raise ValueError(f"init_to_value: {name} must have {width} coefficients per species, got shape {v.shape}")
-                out[c, off: off + width] = row
-        for k, name in enumerate(("ARU_prob_fp_constant", "ARU_fp_unoccupied")):
-            if name in vals:
-                f = scalar(name)
-                if not 0.0 < f < 1.0:
-                    raise ValueError(f"init_to_value: {name} must lie in (0, 1)")
-                out[c, o + k] = np.log(f) - np.log1p(-f)
-        if "mu0" in vals:
-            out[c, o + 2] = scalar("mu0")
-        if "mu1" in vals:
-            gap = scalar("mu1") - out[c, o + 2]
-            if not gap > 0.0:
-                raise ValueError("init_to_value: mu1 must exceed mu0 (its prior is truncated below at mu0)")
-            out[c, o + 3] = np.log(gap)
-        for k, name in enumerate(("sigma0", "sigma1")):
-            if name in vals:
-                sd = scalar(name)
-                if not sd > 0.0:
-                    raise ValueError(f"init_to_value: {name} must be positive")
-                out[c, o + 4 + k] = np.log(sd)
-    return out
+    """Start positions for occu_comb (one species per launch).  ``init_to_value`` takes the reference's site names with constrained
+    values (``ARU_prob_fp_constant``, ``ARU_fp_unoccupied``, ``mu0``, ``mu1``, ``sigma0``, ``sigma1``: a scalar, or one value per
+    species; the coefficients as ``(n_species, K + 1)`` or one row); everything not named starts as ``init_to_uniform``."""
+    layout = layout_for(SimpleNamespace(model="occu_comb", extras={}), N=0, T=0, J=0, Ks=Ks, Ko=Kpc, Ka=Karu)
+    return _start_positions(strategy, layout, D=layout.D, priors=None, num_chains=num_chains, first_chain=first_chain, seed=seed, species=species)

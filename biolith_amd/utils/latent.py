@@ -13,8 +13,10 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from .data import prepare_data
+from .data import prepare_data, species_dataset
+from .layout import draws_from_sites, layout_for
 from .mcmc import LazySamples
+from .misc import time_limit
 
 SERVED = ("occu", "occu_comb")
 
@@ -76,52 +78,34 @@ def conditional_occupancy(
     if n_species != spec.obs.shape[0] or beta.shape[2] != spec.site_covs.shape[1] + 1:
         raise ValueError("conditional_occupancy(): the data differ from the fitted model's (species or site covariate count)")
 
-    from ..engine import OccuDataset
-    from .fit import comb_dataset, comb_engine_draws, engine_options
-
     X = np.asarray(spec.site_covs, dtype=np.float32)
     site_nan = np.isnan(X).any(-1)
+    n_obs = _unmasked(spec.obs, spec.obs_covs, site_nan)
+    ex = spec.extras
     if spec.model == "occu_comb":
-        ex = spec.extras
         sc_ok = ~(np.isnan(ex["scores_obs"]) | site_nan[None, :, None, None])
-        n_obs = _unmasked(spec.obs, spec.obs_covs, site_nan) + _unmasked(ex["ARU_obs"], ex["ARU_obs_covs"], site_nan) + sc_ok.sum(-1)
-        draws_of = lambda sp: comb_engine_draws(posterior, sp)
-        make = lambda sp: comb_dataset(spec, sp, device)
-    else:
-        from .predict import engine_draws
+        n_obs = n_obs + _unmasked(ex["ARU_obs"], ex["ARU_obs_covs"], site_nan) + sc_ok.sum(-1)
+    elif np.asarray(posterior["alpha"]).shape[2] != spec.obs_covs.shape[3] + 1:
+        raise ValueError("conditional_occupancy(): covariate counts differ from the fitted model's coefficients")
+    N, T, J, Ko = spec.obs_covs.shape
+    layout = layout_for(spec, N=N, T=T, J=J, Ks=X.shape[1], Ko=Ko, Ka=ex["ARU_obs_covs"].shape[3] if spec.model == "occu_comb" else None)
 
-        if np.asarray(posterior["alpha"]).shape[2] != spec.obs_covs.shape[3] + 1:
-            raise ValueError("conditional_occupancy(): covariate counts differ from the fitted model's coefficients")
-        n_obs = _unmasked(spec.obs, spec.obs_covs, site_nan)
-        _, _, draws_of = engine_draws(spec, posterior, n)
-        make = lambda sp: OccuDataset(spec.site_covs, spec.obs_covs, spec.obs[sp:sp + 1], spec.prior_beta, spec.prior_alpha,
-                                      device=device, model=spec.model, **engine_options(spec))
-
-    def run():
-        psi, ll, q, z = [], [], [], []
+    psi, ll, q, z = [], [], [], []
+    with time_limit(timeout):
         for sp in range(n_species):
-            ds = make(sp)
-            draws = draws_of(sp)
-            if spec.model == "occu_comb":   # (bl_deterministic does not serve occu_comb: psi as fit._assemble_comb forms it)
-                lin = draws[:, :1] + draws[:, 1:X.shape[1] + 1] @ np.nan_to_num(X).T
-                p = (1.0 / (1.0 + np.exp(-lin))).astype(np.float32)
+            ds, draws = species_dataset(spec, sp, device), draws_from_sites(layout, posterior, sp)
+            if spec.model == "occu_comb":   # (bl_deterministic does not serve occu_comb: psi as fit forms it, from the beta block)
+                blk = layout["beta"]
+                coef = draws[:, blk.offset: blk.offset + blk.width]
+                p = (1.0 / (1.0 + np.exp(-(coef[:, :1] + coef[:, 1:] @ np.nan_to_num(X).T)))).astype(np.float32)
                 psi.append(np.ascontiguousarray(np.broadcast_to(p[:, None], (n, ds.T, ds.N))))
             else:
                 psi.append(ds.deterministic(draws, psi=True, prob_detection=False)[0])
-            a, b, c = ds.site_posterior(draws, seed=(int(random_seed) + (sp << 32)) & (2 ** 64 - 1))
-            ll.append(a)
-            q.append(b)
-            z.append(c)
+            log_lik, z_prob, z_draw = ds.site_posterior(draws, seed=(int(random_seed) + (sp << 32)) & (2 ** 64 - 1))
+            ll.append(log_lik)
+            q.append(z_prob)
+            z.append(z_draw)
             ds.close()
-        return psi, ll, q, z
-
-    if timeout is not None:
-        from .misc import time_limit
-
-        with time_limit(timeout):
-            psi, ll, q, z = run()
-    else:
-        psi, ll, q, z = run()
     out = LazySamples()
     out["psi"] = np.stack(psi, axis=-1)                                   # (n, T, N, S)
     out["z_prob"] = np.stack(q, axis=-1)

@@ -14,7 +14,7 @@ class TimeoutException(Exception):
 
 
 class time_limit:
-    """Context manager: raise :class:`TimeoutException` in the main thread once ``seconds`` have elapsed.
+    """Context manager: raise :class:`TimeoutException` in the main thread once ``seconds`` have elapsed (``None``: no limit).
 
     Uses the real-time interval timer (fractional seconds are honoured) and restores the previous SIGALRM
     disposition on exit.  Outside the main thread signals cannot be delivered; the block then runs unarmed
@@ -22,7 +22,7 @@ class time_limit:
     """
 
     def __init__(self, seconds):
-        self.seconds = float(seconds)
+        self.seconds = 0.0 if seconds is None else float(seconds)
         self._armed = False
         self._previous = None
 

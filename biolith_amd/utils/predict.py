@@ -13,50 +13,10 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from .data import prepare_data, rename_samples
+from .data import prepare_data, rename_samples, species_dataset
+from .layout import draws_from_sites, fp_rate, layout_for
 from .mcmc import LazySamples
-
-
-def engine_draws(spec, posterior, n):
-    """Posterior sites -> the engine's coordinates, one species per handle: ``(fp_site, rate, draws_of)`` with ``draws_of(sp)`` the
-    (n, D) float32 matrix [beta, alpha, (phi), (log sds), (effects)] of species ``sp`` (the layout fit._assemble reads back), ``fp_site``
-    the name of the sampled false-positive rate (or None) and ``rate`` its draws.  Shared by ``predict`` and
-    ``latent.conditional_occupancy``."""
-    beta = np.asarray(posterior["beta"], dtype=np.float32)    # (n, S, Ks+1)
-    alpha = np.asarray(posterior["alpha"], dtype=np.float32)  # (n, S, Ko+1)
-    rate = phi = None
-    fp_site = f"prob_fp_{spec.extras['fp_mode']}" if spec.model == "occu_fp" else None
-    if spec.model in ("occu_re", "occu_rn") and spec.extras.get("re_fp_mode") is not None:   # (random effects +) a false-positive rate: [beta, alpha, phi, log sds, effects]
-        fp_site = f"prob_fp_{spec.extras['re_fp_mode']}"
-    if fp_site is not None:
-        rate = np.clip(np.asarray(posterior[fp_site], dtype=np.float64).reshape(n), 1e-300, 1 - 1e-16)
-        phi = np.log(rate / (1.0 - rate)).astype(np.float32)[:, None]   # the engine's coordinate: logit(rate)
-    if spec.model == "occu_cop" and spec.extras["fp_mode"] is not None:
-        fp_site = f"rate_fp_{spec.extras['fp_mode']}"
-        rate = np.maximum(np.asarray(posterior[fp_site], dtype=np.float64).reshape(n), 1e-300)
-        phi = np.log(rate).astype(np.float32)[:, None]                  # the engine's coordinate: log(rate)
-
-    def re_block(sp):
-        """The random-effects coordinates of species ``sp`` in the engine's one-species layout (see fit._assemble)."""
-        if spec.model != "occu_re" and not (spec.model in ("occu_rn", "nmixture", "occu_cop") and "site_random_effects" in spec.extras):
-            return None
-        cols = []
-        if spec.extras["site_random_effects"]:
-            cols.append(np.log(np.maximum(np.asarray(posterior["site_re_sd"], dtype=np.float64).reshape(n, 1), 1e-300)))
-        if spec.extras["obs_random_effects"]:
-            cols.append(np.log(np.maximum(np.asarray(posterior["obs_re_sd"], dtype=np.float64).reshape(n, 1), 1e-300)))
-        if spec.extras["site_random_effects"]:   # (n, N, species)
-            first = "site_re_abu" if spec.model in ("occu_rn", "nmixture") else "site_re_occ"   # (occu_rn.py:172-176, nmixture.py:166-169)
-            cols += [np.asarray(posterior[first])[..., sp].reshape(n, -1), np.asarray(posterior["site_re_det"])[..., sp].reshape(n, -1)]
-        if spec.extras["obs_random_effects"]:   # (n, J, T, N, species) -> [N][T][J]
-            cols.append(np.asarray(posterior["obs_re"])[..., sp].transpose(0, 3, 2, 1).reshape(n, -1))
-        return np.concatenate(cols, axis=1).astype(np.float32) if cols else None   # (occu_rn with a false-positive rate and no effects)
-
-    def draws_of(sp):
-        rb = re_block(sp)
-        return np.concatenate([beta[:, sp, :], alpha[:, sp, :]] + ([phi] if fp_site else []) + ([rb] if rb is not None else []), axis=1)
-
-    return fp_site, rate, draws_of
+from .misc import time_limit
 
 
 def predict(
@@ -136,33 +96,17 @@ def predict(
     if beta.shape[2] != spec.site_covs.shape[1] + 1 or alpha.shape[2] != spec.obs_covs.shape[3] + 1:
         raise ValueError("predict(): covariate counts differ from the fitted model's coefficients")
 
-    from ..engine import OccuDataset
-    from .fit import engine_options
-
-    fp_site, rate, draws_of = engine_draws(spec, posterior, n)
+    N, T, J = spec.obs_covs.shape[:3]
+    layout = layout_for(spec, N=N, T=T, J=J, Ks=beta.shape[2] - 1, Ko=alpha.shape[2] - 1)
+    fp_site = layout.fp_site
+    rate = fp_rate(layout, posterior) if fp_site else None
 
     if spec.model == "occu_cs":   # sites psi, z, f, s (occu_cs.py:196-232); mu / sigma travel in the engine's coordinates
-        from ..engine import OccuDataset
-        from .fit import engine_options
-
         post = {k: np.asarray(posterior[k], dtype=np.float64).reshape(n) for k in ("mu0", "mu1", "sigma0", "sigma1")}
-        extra = np.stack([post["mu0"], np.log(np.maximum(post["mu1"] - post["mu0"], 1e-300)), np.log(post["sigma0"]),
-                          np.log(post["sigma1"])], axis=1).astype(np.float32)
-        ds = OccuDataset(spec.site_covs, spec.obs_covs, spec.obs, spec.prior_beta, spec.prior_alpha, device=device, model="occu_cs",
-                         **engine_options(spec))
-        draws = np.concatenate([beta[:, 0, :], alpha[:, 0, :], extra], axis=1)
-
-        def run_cs():
+        with time_limit(timeout):
+            ds, draws = species_dataset(spec, 0, device), draws_from_sites(layout, posterior, 0)
             psi = ds.deterministic(draws, psi=True, prob_detection=False)[0]
-            return (psi,) + ds.predictive_scores(draws, seed=int(random_seed) & (2 ** 64 - 1))
-
-        if timeout is not None:
-            from .misc import time_limit
-
-            with time_limit(timeout):
-                psi, z, f, s = run_cs()
-        else:
-            psi, z, f, s = run_cs()
+            z, f, s = ds.predictive_scores(draws, seed=int(random_seed) & (2 ** 64 - 1))
         out = LazySamples()
         out["psi"], out["z"] = psi[..., None], z[..., None].astype(np.int32)
         out["f"], out["s"] = f[..., None].astype(np.int32), s[..., None]
@@ -170,26 +114,15 @@ def predict(
             out[k] = v.astype(np.float32)
         return rename_samples(out, site_names, obs_names)
 
-    def run():
-        handles, first, latent, y8 = [], [], [], []
+    handles, first, latent, y8 = [], [], [], []
+    with time_limit(timeout):
         for sp in range(n_species):
-            ds = OccuDataset(spec.site_covs, spec.obs_covs, spec.obs[sp:sp + 1], spec.prior_beta, spec.prior_alpha,
-                             device=device, model=spec.model, **engine_options(spec))
-            draws = draws_of(sp)
+            ds, draws = species_dataset(spec, sp, device), draws_from_sites(layout, posterior, sp)
             first.append(ds.deterministic(draws, psi=True, prob_detection=False)[0])
             lat, yy = ds.predictive(draws, seed=(int(random_seed) + (sp << 32)) & (2 ** 64 - 1))
             latent.append(lat)
             y8.append(yy)
             handles.append((ds, draws))
-        return handles, first, latent, y8
-
-    if timeout is not None:
-        from .misc import time_limit
-
-        with time_limit(timeout):
-            handles, first, latent, y8 = run()
-    else:
-        handles, first, latent, y8 = run()
 
     rn = spec.model in ("occu_rn", "nmixture")   # the abundance models: sites "abundance" and "N_i"
     out = LazySamples()
