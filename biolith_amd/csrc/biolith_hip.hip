@@ -21,6 +21,7 @@
 #include "nuts_kernel.hpp"
 #include "pred_rng.hpp"
 #include "site_posterior.hpp"
+#include "abundance_posterior.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -471,6 +472,72 @@ extern "C" int bl_site_posterior(bl_dataset *ds, int n_draws, const float *draws
         if (log_lik) BL_HIP(hipMemcpy(log_lik + (size_t)n0 * cells, d_ll, (size_t)(n1 - n0) * cells * 4, hipMemcpyDeviceToHost));
         if (z_prob) BL_HIP(hipMemcpy(z_prob + (size_t)n0 * cells, d_q, (size_t)(n1 - n0) * cells * 4, hipMemcpyDeviceToHost));
         if (z) BL_HIP(hipMemcpy(z + (size_t)n0 * cells, d_z, (size_t)(n1 - n0) * cells, hipMemcpyDeviceToHost));
+    }
+    return BL_OK;
+}
+
+// ---- conditional abundance: P(N | data), the site-period log-likelihood and a draw of N, per posterior draw ----
+// (BUILDER-DEFINED: the reference's predict withholds the observations.)  Kernel: abundance_posterior.hip.  It reads the rows the
+// samplers read -- occu_rn's sign-folded visits, nmixture's (m y, m, w..) visits, largest-count rows and table of log-binomial sums --
+// so nothing is uploaded; a draw's layout is bl_predict's / bl_predict_counts'.
+extern "C" int bl_abundance_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *n_mean,
+                                      float *occ_prob, int32_t *n_draw)
+{
+    if (!ds || !draws || n_draws <= 0 || (!log_lik && !n_mean && !occ_prob && !n_draw))
+        return bl_fail(BL_ERR_INVALID, "bl_abundance_posterior: bad argument");
+    if (ds->nsp > 1) return bl_fail(BL_ERR_UNSUPPORTED, "bl_abundance_posterior: a joint-species handle samples; use one handle per species");
+    const char *refused = nullptr;
+    if (ds->model == 0) refused = "occu";
+    else if (ds->model == 2) refused = "occu with false positives";
+    else if (ds->model == 3) refused = "occu_cop";
+    else if (ds->model == 8) refused = "occu_dyn";
+    else if (ds->model == 6) {
+        const int k = ds->re.kind;
+        refused = (k == 0 || k == 2) ? "occu with random effects" : k == 1 ? "occu_cs" : (k == 6 || k == 7) ? "occu_cop" : k == 8 ? "occu_comb"
+                  : (k == 3 || k == 4 || k == 5) ? nullptr : "this model";
+    } else if (ds->model != 1 && ds->model != 4) refused = "this model";
+    if (refused)
+        return bl_fail(BL_ERR_UNSUPPORTED, "bl_abundance_posterior: not built for %s (occu_rn, with or without a false-positive rate / random effects, "
+                       "and nmixture, with or without random effects)", refused);
+    if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
+    int rc = set_device(ds);
+    if (rc) return rc;
+    const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates, D = ds->D;
+    BlAbundPostParams p{};
+    p.rows = ds->d_rows; p.ns = ds->n_stride; p.N = N; p.T = T; p.J = J; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = D;
+    p.r0 = ds->KS; p.vw = ds->KO + 2; p.o_al = ds->Ks + 1; p.seed = (unsigned long long)seed;
+    p.o_fp = p.o_u = p.o_v = p.o_e = -1;
+    p.nmix = (ds->model == 4 || (ds->model == 6 && ds->re.kind == 3)) ? 1 : 0;
+    p.K = ds->model == 6 ? ds->re.max_abundance : ds->max_abundance;
+    p.tab = p.nmix ? ds->d_tab : nullptr;
+    p.r_ymax = ds->KS + T * J * p.vw;
+    if (ds->model == 6) {
+        const BlReModel &m = ds->re;
+        if (m.kind == 5) p.o_fp = m.o_fp;
+        p.o_u = m.o_u; p.o_v = m.o_v; p.o_e = m.o_e;
+    }
+    if (p.K < 1 || p.K >= BL_RN_NB || (p.nmix && !p.tab)) return bl_fail(BL_ERR_INVALID, "bl_abundance_posterior: the handle carries no abundance table");
+    float *d_draws = nullptr, *d_ll = nullptr, *d_mean = nullptr, *d_occ = nullptr;
+    int *d_n = nullptr;
+    DevScratch scratch;
+    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * D * 4));
+    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * D * 4, hipMemcpyHostToDevice));
+    const size_t cells = (size_t)T * N; // per draw; every output is 4 bytes a cell
+    int chunk = (int)std::min<size_t>((size_t)n_draws, std::max<size_t>(1, ((size_t)256 << 20) / (cells * 4)));
+    if (log_lik) BL_HIP(scratch.alloc((void **)&d_ll, (size_t)chunk * cells * 4));
+    if (n_mean) BL_HIP(scratch.alloc((void **)&d_mean, (size_t)chunk * cells * 4));
+    if (occ_prob) BL_HIP(scratch.alloc((void **)&d_occ, (size_t)chunk * cells * 4));
+    if (n_draw) BL_HIP(scratch.alloc((void **)&d_n, (size_t)chunk * cells * 4));
+    p.draws = d_draws; p.log_lik = d_ll; p.n_mean = d_mean; p.occ_prob = d_occ; p.n_draw = d_n;
+    for (int n0 = 0; n0 < n_draws; n0 += chunk) {
+        const int n1 = (n0 + chunk < n_draws) ? n0 + chunk : n_draws;
+        p.n0 = n0; p.n1 = n1;
+        BL_HIP((hipError_t)bl_launch_abundance_posterior(&p, (n1 - n0) < 1024 ? (n1 - n0) : 1024, nullptr));
+        const size_t off = (size_t)n0 * cells, bytes = (size_t)(n1 - n0) * cells * 4;
+        if (log_lik) BL_HIP(hipMemcpy(log_lik + off, d_ll, bytes, hipMemcpyDeviceToHost));
+        if (n_mean) BL_HIP(hipMemcpy(n_mean + off, d_mean, bytes, hipMemcpyDeviceToHost));
+        if (occ_prob) BL_HIP(hipMemcpy(occ_prob + off, d_occ, bytes, hipMemcpyDeviceToHost));
+        if (n_draw) BL_HIP(hipMemcpy(n_draw + off, d_n, bytes, hipMemcpyDeviceToHost));
     }
     return BL_OK;
 }

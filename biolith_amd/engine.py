@@ -500,6 +500,25 @@ class OccuDataset:
             _PINNED.kick(self._lib)
         return out_l, out_q, out_z
 
+    def abundance_posterior(self, draws, seed: int = 0, log_lik: bool = True, n_mean: bool = True, occ_prob: bool = True, n_draw: bool = True):
+        """Conditional abundance for draws (n, D), each output (n, T, N): ``log_lik`` float32, the N-marginalised log-likelihood of a
+        (period, site)'s unmasked observations; ``n_mean`` float32 = E[N | those observations, theta]; ``occ_prob`` float32 =
+        P(N > 0 | those observations, theta); ``n_draw`` int32, one draw of N given them, a function of (seed, draw, period, site).
+        occu_rn (false-positive rate, random effects) and nmixture (random effects) handles (include/biolith_hip.h:
+        bl_abundance_posterior); no counterpart in the reference."""
+        d = self._draw_matrix(draws)
+        n = d.shape[0]
+        shape = (n, self.T, self.N)
+        out_l = self._big_empty(shape) if log_lik else None
+        out_m = self._big_empty(shape) if n_mean else None
+        out_q = self._big_empty(shape) if occ_prob else None
+        out_n = self._big_empty(shape, np.int32) if n_draw else None
+        if n:
+            i32 = None if out_n is None else out_n.ctypes.data_as(C.POINTER(C.c_int32))
+            _ffi.check(self._lib.bl_abundance_posterior(self._h, n, _fp(d), C.c_uint64(int(seed) & (2 ** 64 - 1)), _fp(out_l), _fp(out_m), _fp(out_q), i32))
+            _PINNED.kick(self._lib)
+        return out_l, out_m, out_q, out_n
+
 
 def _predictive_scores(self, draws, seed: int = 0):
     """occu_cs: posterior predictive ``z`` (n, T, N), ``f`` (n, J, T, N) as uint8 and the scores ``s`` (n, J, T, N) float32

@@ -5,6 +5,10 @@ replicate given a ``z`` drawn from the PRIOR, so the criterion carries the Monte
 sums out analytically.  Here the unit is the (site, period) -- the level at which the marginal likelihood factorises -- and the
 pointwise term is ``latent["log_lik"]`` of :func:`biolith_amd.utils.conditional_occupancy`: log(psi p(obs | 1) + (1 - psi) p(obs | 0)).
 Cells without an unmasked observation (``n_obs == 0``) carry no likelihood and are left out.
+
+The result of :func:`biolith_amd.utils.conditional_abundance` (``occu_rn`` / ``nmixture``) is accepted too: its ``log_lik`` is the same
+kind of term with the abundance N summed out, its ``n_obs`` the same count, so an ``occu`` and an ``occu_rn`` fit of the same detections
+compare on the same cells.
 """
 from __future__ import annotations
 
@@ -16,7 +20,7 @@ from .predictive_density import _pointwise
 
 
 def _cells(latent) -> np.ndarray:
-    """(draws, cells with n_obs > 0) float64 of a ``conditional_occupancy`` result."""
+    """(draws, cells with n_obs > 0) float64 of a ``conditional_occupancy`` / ``conditional_abundance`` result."""
     ll = np.asarray(latent["log_lik"], dtype=np.float64)
     n_obs = np.asarray(latent["n_obs"])
     if ll.shape[1:] != n_obs.shape:
@@ -25,12 +29,14 @@ def _cells(latent) -> np.ndarray:
 
 
 def lppd_marginal(latent) -> float:
-    """``sum_cells log mean_draws exp(log_lik)`` over the (period, site, species) cells with data."""
+    """``sum_cells log mean_draws exp(log_lik)`` over the (period, site, species) cells with data; ``latent`` is the result of
+    ``conditional_occupancy`` or of ``conditional_abundance``."""
     return _pointwise(_cells(latent))[0]
 
 
 def waic_marginal(latent) -> Dict[str, float]:
-    """``{"waic": -2 (lppd - p_waic), "p_waic", "lppd"}`` with the site-period as the unit (p_waic: the summed posterior variance)."""
+    """``{"waic": -2 (lppd - p_waic), "p_waic", "lppd"}`` with the site-period as the unit (p_waic: the summed posterior variance);
+    ``latent`` is the result of ``conditional_occupancy`` or of ``conditional_abundance``."""
     l, p = _pointwise(_cells(latent))
     return {"waic": -2 * (l - p), "p_waic": p, "lppd": l}
 
@@ -38,3 +44,9 @@ def waic_marginal(latent) -> Dict[str, float]:
 def finite_sample_occupancy(latent) -> np.ndarray:
     """(draws, T, S): the share of occupied sites in each conditional draw of ``z`` -- the finite-sample occupancy of Royle & Kery."""
     return np.asarray(latent["z"], dtype=np.float64).mean(axis=2)
+
+
+def finite_sample_abundance(latent) -> np.ndarray:
+    """(draws, T, S): the total of ``N_i`` over the sites in each conditional draw of a ``conditional_abundance`` result -- the
+    finite-sample population size of the surveyed sites."""
+    return np.asarray(latent["N_i"], dtype=np.float64).sum(axis=2)

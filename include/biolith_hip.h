@@ -379,6 +379,25 @@ int bl_predict_scores(bl_dataset *ds, int n_draws, const float *draws, uint64_t 
 int bl_site_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *z_prob, uint8_t *z);
 
 /*
+ * Conditional abundance -- BUILDER-DEFINED, NO REFERENCE COUNTERPART (biolith/utils/predict.py withholds the observations, so its N_i
+ * is drawn from the prior Poisson).  Per posterior draw and (period, site), with l_n the log of the n-th addend of the model's own
+ * marginal likelihood over the site-period's unmasked replicates and K = max_abundance:
+ *   occu_rn   l_n = log Categorical(Poisson(lambda) pmf renormalised on 0..K)(n) + sum_j log Bernoulli(y_j; 1 - (1 - p_nj)(1 - f)),
+ *             p_nj = 1 - (1 - r_j)^n, f the false-positive rate or 0, probabilities clamped to [tiny, 1 - eps] as bl_logp_grad clamps them
+ *   nmixture  l_n = log Poisson(lambda)(n) + sum_j log Binomial(y_j; n, p_j) for max_j y_j <= n <= K, -inf below (the untruncated Poisson
+ *             cut at K, as the model's N_i_trunc_norm factor leaves it)
+ *   log_lik  [n_draws][T][N] = logsumexp_n l_n:   sum over cells = the likelihood part of -U of bl_logp_grad
+ *   n_mean   [n_draws][T][N] = sum_n n exp(l_n - log_lik) = E[N | obs, theta]
+ *   occ_prob [n_draws][T][N] = 1 - exp(l_0 - log_lik) = P(N > 0 | obs, theta)
+ *   n_draw   [n_draws][T][N] ~ exp(l_n - log_lik) by inversion, a function of (seed, draw, period, site) only (bl_predict's generator)
+ * A cell with no unmasked observation returns the prior: occu_rn log_lik = 0 exactly, nmixture log_lik = log P(N <= K).  Host memory,
+ * NULL = skip.  draws [n_draws][D] float32 as for bl_predict / bl_predict_counts.  Serves one-species handles of bl_dataset_create_rn,
+ * _rn_re, _rn_fp, _nmix and _nmix_re; every other handle: BL_ERR_UNSUPPORTED, the message names the model.
+ */
+int bl_abundance_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *n_mean, float *occ_prob,
+                           int32_t *n_draw);
+
+/*
  * Multi-GPU: chain-parallel sampling and the gather of the draws.
  *
  * The reference's only multi-device strategy is chain_method="parallel" (biolith/utils/fit.py:109-113: one chain per
