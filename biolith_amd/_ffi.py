@@ -73,7 +73,7 @@ EXPORTS = (
     "bl_nuts_geometry", "bl_nuts_lane_group", "bl_nuts_kernel_name", "bl_nuts_debug_counters", "bl_deterministic", "bl_predict", "bl_predict_counts", "bl_predict_scores", "bl_dataset_create_fp", "bl_dataset_create_cop", "bl_dataset_create_nmix", "bl_dataset_create_re", "bl_dataset_create_re_fp", "bl_dataset_create_nmix_re", "bl_dataset_create_rn_re", "bl_dataset_create_rn_fp", "bl_dataset_create_cop_re", "bl_dataset_create_cs", "bl_dataset_create_comb", "bl_dataset_set_prior_family", "bl_rng_streams", "bl_adaptation_schedule",
     "bl_comm_rccl_version", "bl_comm_unique_id", "bl_comm_init_rank", "bl_comm_init_all", "bl_comm_info", "bl_comm_destroy",
     "bl_gather_draws", "bl_result_block_layout", "bl_gather_unpack", "bl_host_alloc", "bl_host_free",
-    "bl_nuts_env_overrides", "bl_env_overrides", "bl_site_posterior", "bl_abundance_posterior",
+    "bl_nuts_env_overrides", "bl_env_overrides", "bl_site_posterior", "bl_abundance_posterior", "bl_path_posterior",
 )
 
 _lib = None
@@ -153,6 +153,7 @@ def load():
         L.bl_predict_scores.argtypes = [vp, C.c_int, fp, C.c_uint64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), fp]
         L.bl_site_posterior.argtypes = [vp, C.c_int, fp, C.c_uint64, fp, fp, C.POINTER(C.c_uint8)]
         L.bl_abundance_posterior.argtypes = [vp, C.c_int, fp, C.c_uint64, fp, fp, fp, C.POINTER(C.c_int32)]
+        L.bl_path_posterior.argtypes = [vp, C.c_int, fp, C.c_uint64, fp, fp, fp, fp, C.POINTER(C.c_uint8)]
         L.bl_rng_streams.argtypes = [C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
         L.bl_adaptation_schedule.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
         u8p = C.POINTER(C.c_uint8)

@@ -22,6 +22,7 @@
 #include "pred_rng.hpp"
 #include "site_posterior.hpp"
 #include "abundance_posterior.hpp"
+#include "path_posterior.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -538,6 +539,66 @@ extern "C" int bl_abundance_posterior(bl_dataset *ds, int n_draws, const float *
         if (n_mean) BL_HIP(hipMemcpy(n_mean + off, d_mean, bytes, hipMemcpyDeviceToHost));
         if (occ_prob) BL_HIP(hipMemcpy(occ_prob + off, d_occ, bytes, hipMemcpyDeviceToHost));
         if (n_draw) BL_HIP(hipMemcpy(n_draw + off, d_n, bytes, hipMemcpyDeviceToHost));
+    }
+    return BL_OK;
+}
+
+// ---- conditional dynamics: the smoothed P(z_t | all seasons' data), the transitions' pairwise terms, the site log-likelihood and a
+// joint draw of the path, per posterior draw ----
+// (BUILDER-DEFINED, like the model.)  Kernel: path_posterior.hip.  It reads the sign-folded visit rows of the occu_dyn handle, so nothing
+// is uploaded; a draw's layout is the sampler's, [b_psi | b_col | b_ext | alpha].  The device z_prob buffer doubles as the kernel's
+// workspace (the filtered log-odds), so it is allocated whether or not the caller wants z_prob back.
+extern "C" int bl_path_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *z_prob,
+                                 float *col_prob, float *ext_prob, uint8_t *z)
+{
+    if (!ds || !draws || n_draws <= 0 || (!log_lik && !z_prob && !col_prob && !ext_prob && !z))
+        return bl_fail(BL_ERR_INVALID, "bl_path_posterior: bad argument");
+    if (ds->nsp > 1)
+        return bl_fail(BL_ERR_UNSUPPORTED, "bl_path_posterior: a joint-species handle samples and is not occu_dyn; use bl_site_posterior on one handle per species");
+    const char *refused = nullptr;
+    if (ds->model == 0) refused = "occu";
+    else if (ds->model == 1) refused = "occu_rn";
+    else if (ds->model == 2) refused = "occu_fp (occu with false positives)";
+    else if (ds->model == 3) refused = "occu_cop";
+    else if (ds->model == 4) refused = "nmixture";
+    else if (ds->model == 6) {
+        const int k = ds->re.kind;
+        refused = (k == 0 || k == 2) ? "occu_re (occu with random effects)" : k == 1 ? "occu_cs" : k == 3 ? "nmixture" : (k == 4 || k == 5) ? "occu_rn"
+                  : (k == 6 || k == 7) ? "occu_cop" : k == 8 ? "occu_comb" : "this model";
+    } else if (ds->model != 8) refused = "this model";
+    if (refused)
+        return bl_fail(BL_ERR_UNSUPPORTED, "bl_path_posterior: not built for %s (occu_dyn only; the static models' conditionals are "
+                       "bl_site_posterior / bl_abundance_posterior)", refused);
+    if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
+    int rc = set_device(ds);
+    if (rc) return rc;
+    const int N = ds->dims.n_sites, T = ds->dims.n_periods, D = ds->D;
+    BlPathPostParams p{};
+    p.rows = ds->d_rows; p.ns = ds->n_stride; p.N = N; p.T = T; p.J = ds->dims.n_replicates; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = D;
+    p.r0 = ds->KS; p.vw = ds->KO + 1; p.seed = (unsigned long long)seed;
+    float *d_draws = nullptr, *d_ll = nullptr, *d_q = nullptr, *d_col = nullptr, *d_ext = nullptr;
+    unsigned char *d_z = nullptr;
+    DevScratch scratch;
+    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * D * 4));
+    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * D * 4, hipMemcpyHostToDevice));
+    const size_t cells = (size_t)T * N, pairs = (size_t)(T - 1) * N; // per draw; the largest output is 4 bytes a cell
+    int chunk = (int)std::min<size_t>((size_t)n_draws, std::max<size_t>(1, ((size_t)256 << 20) / (cells * 4)));
+    if (log_lik) BL_HIP(scratch.alloc((void **)&d_ll, (size_t)chunk * N * 4));
+    BL_HIP(scratch.alloc((void **)&d_q, (size_t)chunk * cells * 4));
+    if (col_prob && pairs) BL_HIP(scratch.alloc((void **)&d_col, (size_t)chunk * pairs * 4));
+    if (ext_prob && pairs) BL_HIP(scratch.alloc((void **)&d_ext, (size_t)chunk * pairs * 4));
+    if (z) BL_HIP(scratch.alloc((void **)&d_z, (size_t)chunk * cells));
+    p.draws = d_draws; p.log_lik = d_ll; p.z_prob = d_q; p.col_prob = d_col; p.ext_prob = d_ext; p.z = d_z;
+    for (int n0 = 0; n0 < n_draws; n0 += chunk) {
+        const int n1 = (n0 + chunk < n_draws) ? n0 + chunk : n_draws;
+        const size_t m = (size_t)(n1 - n0);
+        p.n0 = n0; p.n1 = n1;
+        BL_HIP((hipError_t)bl_launch_path_posterior(&p, (n1 - n0) < 1024 ? (n1 - n0) : 1024, nullptr));
+        if (log_lik) BL_HIP(hipMemcpy(log_lik + (size_t)n0 * N, d_ll, m * N * 4, hipMemcpyDeviceToHost));
+        if (z_prob) BL_HIP(hipMemcpy(z_prob + (size_t)n0 * cells, d_q, m * cells * 4, hipMemcpyDeviceToHost));
+        if (d_col) BL_HIP(hipMemcpy(col_prob + (size_t)n0 * pairs, d_col, m * pairs * 4, hipMemcpyDeviceToHost));
+        if (d_ext) BL_HIP(hipMemcpy(ext_prob + (size_t)n0 * pairs, d_ext, m * pairs * 4, hipMemcpyDeviceToHost));
+        if (z) BL_HIP(hipMemcpy(z + (size_t)n0 * cells, d_z, m * cells, hipMemcpyDeviceToHost));
     }
     return BL_OK;
 }

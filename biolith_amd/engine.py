@@ -519,6 +519,27 @@ class OccuDataset:
             _PINNED.kick(self._lib)
         return out_l, out_m, out_q, out_n
 
+    def path_posterior(self, draws, seed: int = 0, log_lik: bool = True, z_prob: bool = True, col_prob: bool = True, ext_prob: bool = True,
+                       z: bool = True):
+        """Conditional dynamics of an occu_dyn handle for draws (n, D): ``log_lik`` (n, N) float32, the site's path-marginalised
+        log-likelihood; ``z_prob`` (n, T, N) float32 = P(z_t = 1 | all seasons' data, theta), the smoothed marginal; ``col_prob`` /
+        ``ext_prob`` (n, T - 1, N) float32 = P(z_t = 0, z_t+1 = 1 | .) / P(z_t = 1, z_t+1 = 0 | .); ``z`` (n, T, N) uint8, one joint
+        draw of the path by forward filtering, backward sampling, a function of (seed, draw, period, site)
+        (include/biolith_hip.h: bl_path_posterior); builder-defined like the model."""
+        d = self._draw_matrix(draws)
+        n = d.shape[0]
+        out_l = self._big_empty((n, self.N)) if log_lik else None
+        out_q = self._big_empty((n, self.T, self.N)) if z_prob else None
+        out_c = self._big_empty((n, self.T - 1, self.N)) if col_prob else None
+        out_e = self._big_empty((n, self.T - 1, self.N)) if ext_prob else None
+        out_z = np.empty((n, self.T, self.N), dtype=np.uint8) if z else None
+        if n:
+            u8 = None if out_z is None else out_z.ctypes.data_as(C.POINTER(C.c_uint8))
+            _ffi.check(self._lib.bl_path_posterior(self._h, n, _fp(d), C.c_uint64(int(seed) & (2 ** 64 - 1)), _fp(out_l), _fp(out_q), _fp(out_c),
+                                                   _fp(out_e), u8))
+            _PINNED.kick(self._lib)
+        return out_l, out_q, out_c, out_e, out_z
+
 
 def _predictive_scores(self, draws, seed: int = 0):
     """occu_cs: posterior predictive ``z`` (n, T, N), ``f`` (n, J, T, N) as uint8 and the scores ``s`` (n, J, T, N) float32

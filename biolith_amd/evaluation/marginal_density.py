@@ -6,6 +6,10 @@ sums out analytically.  Here the unit is the (site, period) -- the level at whic
 pointwise term is ``latent["log_lik"]`` of :func:`biolith_amd.utils.conditional_occupancy`: log(psi p(obs | 1) + (1 - psi) p(obs | 0)).
 Cells without an unmasked observation (``n_obs == 0``) carry no likelihood and are left out.
 
+The result of :func:`biolith_amd.utils.conditional_dynamics` (``occu_dyn``) is accepted too: there the seasons of a site are dependent, the
+marginal likelihood factorises over SITES only, and ``log_lik`` / ``n_obs`` are per site.  ``finite_sample_turnover`` reads its joint
+path draws.
+
 The result of :func:`biolith_amd.utils.conditional_abundance` (``occu_rn`` / ``nmixture``) is accepted too: its ``log_lik`` is the same
 kind of term with the abundance N summed out, its ``n_obs`` the same count, so an ``occu`` and an ``occu_rn`` fit of the same detections
 compare on the same cells.
@@ -50,3 +54,16 @@ def finite_sample_abundance(latent) -> np.ndarray:
     """(draws, T, S): the total of ``N_i`` over the sites in each conditional draw of a ``conditional_abundance`` result -- the
     finite-sample population size of the surveyed sites."""
     return np.asarray(latent["N_i"], dtype=np.float64).sum(axis=2)
+
+
+def finite_sample_turnover(latent) -> Dict[str, np.ndarray]:
+    """``{"colonisation": (draws, T - 1, S), "extinction": (draws, T - 1, S)}`` of a ``conditional_dynamics`` result: per conditional
+    path draw the share of the sites unoccupied at t that are occupied at t + 1, and the share of the sites occupied at t that are
+    unoccupied at t + 1 -- the realised colonisation and extinction rates of the surveyed sites.  NaN where no site is in the
+    denominator."""
+    z = np.asarray(latent["z"]) != 0                                      # (n, T, N, S)
+    now, nxt = z[:, :-1], z[:, 1:]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        col = (~now & nxt).sum(axis=2) / (~now).sum(axis=2).astype(np.float64)
+        ext = (now & ~nxt).sum(axis=2) / now.sum(axis=2).astype(np.float64)
+    return {"colonisation": col, "extinction": ext}

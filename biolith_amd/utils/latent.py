@@ -66,8 +66,9 @@ def conditional_occupancy(
     if name is None:
         raise TypeError("conditional_occupancy(): model_fn must be a biolith_amd model (biolith_amd.models.occu / occu_comb)")
     if name not in SERVED:
+        hint = "; use conditional_dynamics" if name == "occu_dyn" else ""
         raise NotImplementedError(f"conditional_occupancy(): not built for {name} (built: occu with or without false positives / random "
-                                  "effects, and occu_comb)")
+                                  f"effects, and occu_comb){hint}")
     device = int(kwargs.pop("device", 0))
     site_covs, obs_covs, obs, _, _, _ = prepare_data(site_covs, obs_covs, obs, None)
     valid = {k: v for k, v in dict(site_covs=site_covs, obs_covs=obs_covs, obs=obs).items() if v is not None}

@@ -398,6 +398,30 @@ int bl_abundance_posterior(bl_dataset *ds, int n_draws, const float *draws, uint
                            int32_t *n_draw);
 
 /*
+ * Conditional dynamics -- BUILDER-DEFINED, like the model it serves (bl_dataset_create_dyn).  The seasons of a site are dependent, so
+ * this is a forward filter, a backward smoother and, for the joint draw, forward filtering backward sampling; per posterior draw and
+ * site, with a_t = log p(y_t | z_t = 1) over season t's unmasked visits and kb_t = n_detections log tiny (the terms, clamp and masks of
+ * bl_logp_grad), pi_1 = psi:
+ *   forward   A = log pi_t + a_t,  B = log(1 - pi_t) + kb_t,  phi_t = sigmoid(A - B) = P(z_t = 1 | y_1..t),
+ *             pi_t+1 = phi_t (1 - eps) + (1 - phi_t) gamma,   1 - pi_t+1 = phi_t eps + (1 - phi_t)(1 - gamma)   (two positive sums)
+ *   log_lik  [n_draws][N]      = sum_t logaddexp(A, B), the path-marginalised log-likelihood of the SITE (the level at which the dynamic
+ *                                likelihood factorises):   sum over sites = the likelihood part of -U of bl_logp_grad
+ *   z_prob   [n_draws][T][N]   = rho_t = P(z_t = 1 | y_1..T, theta), the smoothed marginal
+ *   col_prob [n_draws][T-1][N] = xi_t(0,1) = P(z_t = 0, z_t+1 = 1 | y_1..T, theta)
+ *   ext_prob [n_draws][T-1][N] = xi_t(1,0) = P(z_t = 1, z_t+1 = 0 | y_1..T, theta)
+ *   z        [n_draws][T][N]   one JOINT draw of the path: z_T ~ Bernoulli(phi_T), z_t | z_t+1 = b ~ Bernoulli(phi_t P(b | 1) /
+ *                                (phi_t P(b | 1) + (1 - phi_t) P(b | 0))); the uniform of cell (draw, t, site) is bl_site_posterior's, so z
+ *                                is a function of (seed, draw, period, site) only
+ * A site with no unmasked observation in any season has log_lik = 0 exactly and z_prob = the propagated prior (psi, then pi_t); a season
+ * with an unmasked detection has z_prob = 1 and z = 1.  Host memory, NULL = skip.  draws [n_draws][D] float32 in the sampler's layout
+ * [b_psi | b_col | b_ext (Ks + 1 each) | alpha (Ko + 1)].  Serves handles of bl_dataset_create_dyn; every other handle:
+ * BL_ERR_UNSUPPORTED, the message names the model (the static models' conditionals are bl_site_posterior / bl_abundance_posterior, which
+ * in turn refuse occu_dyn).
+ */
+int bl_path_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *z_prob, float *col_prob,
+                      float *ext_prob, uint8_t *z);
+
+/*
  * Multi-GPU: chain-parallel sampling and the gather of the draws.
  *
  * The reference's only multi-device strategy is chain_method="parallel" (biolith/utils/fit.py:109-113: one chain per
