@@ -22,21 +22,14 @@
 // What is formed per (n, visit) -- a detection's log(f + (1 - f)(1 - q^n)), a floored non-detection -- is float32.
 #include "abundance_posterior.hpp"
 
-#include "nuts_kernel.hpp"
+#include "posterior_math.hpp"
 #include "pred_rng.hpp"
 
 namespace {
 
-constexpr float AP_TINY = 1.1754944e-38f, AP_ONE_M_EPS = 0.99999988f, AP_LOG_EPS = -15.9423847f;
+constexpr float AP_ONE_M_EPS = 0.99999988f;
 constexpr double AP_CUT = 45.0;
 
-// log(1 + e) for 0 <= e <= 1, relative error of a few ulps also where e is small (log(op) e / (op - 1): the rounding of 1 + e cancels)
-__device__ __forceinline__ float ap_log1p(float e)
-{
-    const float op = 1.0f + e, d = op - 1.0f;
-    const float r = bl_log(op) * (e * bl_rcp(d));
-    return d == 0.0f ? e : r;
-}
 // 1 - e^x for x <= 0 without cancellation: the series of expm1 down to x = -0.5 (|x|^10 / 10! < 3e-10 of x), 1 - e^x below
 __device__ __forceinline__ float ap_one_minus_exp(float x)
 {
@@ -87,9 +80,8 @@ __global__ void bl_abundance_posterior_kernel(const BlAbundPostParams p)
             }
             shift = -(m0 + log(sz));
             if (p.o_fp >= 0) {
-                const float phi = th[p.o_fp], e = bl_exp(-fabsf(phi)), r = bl_rcp(1.0f + e);
-                fpr = (phi > 0.0f ? 1.0f : e) * r;
-                gq = (phi > 0.0f ? e : 1.0f) * r;
+                const float phi = th[p.o_fp];
+                post_sig(phi, fpr, gq);
                 lgqd = -ap_softplus((double)phi);
                 lgq = (float)lgqd;
             }
@@ -155,19 +147,19 @@ __global__ void bl_abundance_posterior_kernel(const BlAbundPostParams p)
                 } else {
                     double s = pois;
                     const float nf = (float)n;
-                    const bool open = fmaf(nf, lqmin, lgq) > AP_LOG_EPS; // no non-detection is at numpyro's floor: rank one in n
+                    const bool open = fmaf(nf, lqmin, lgq) > POST_LOG_EPS; // no non-detection is at numpyro's floor: rank one in n
                     if (open) s += fma((double)n, cnon, a);
                     if (nd > 0.0f || !open)
                         for (int j = 0; j < J; j++) {
                             float c;
                             const float u = visit(j, c);
                             if (c == 0.0f || (c < 0.0f && open)) continue;
-                            const float l1 = ap_log1p(bl_exp(-fabsf(u)));
+                            const float l1 = post_log1p(bl_exp(-fabsf(u)));
                             if (c < 0.0f) {
-                                s += (double)fmaxf(fmaf(nf, fminf(u, 0.0f) - l1, lgq), AP_LOG_EPS);
+                                s += (double)fmaxf(fmaf(nf, fminf(u, 0.0f) - l1, lgq), POST_LOG_EPS);
                             } else { // P(y = 1 | n) = f + (1 - f)(1 - q^n), q^n = e^(n log q), log q = log sigma(-u)
                                 const float pd = ap_one_minus_exp(nf * (fminf(-u, 0.0f) - l1));
-                                s += (double)bl_log(fmaxf(fminf(fmaf(gq, pd, fpr), AP_ONE_M_EPS), AP_TINY));
+                                s += (double)bl_log(fmaxf(fminf(fmaf(gq, pd, fpr), AP_ONE_M_EPS), POST_TINY));
                             }
                         }
                     return s;
@@ -216,8 +208,8 @@ __global__ void bl_abundance_posterior_kernel(const BlAbundPostParams p)
 
 extern "C" int bl_launch_abundance_posterior(const BlAbundPostParams *p, int grid_y, hipStream_t st)
 {
-    const int nt = p->N < 256 ? 64 : 256; // a small data set would idle three quarters of a 256-thread workgroup
-    const dim3 grid((p->N + nt - 1) / nt, grid_y), block(nt);
+    dim3 grid, block;
+    post_geometry(p->N, grid_y, grid, block);
     if (p->nmix) hipLaunchKernelGGL(bl_abundance_posterior_kernel<true>, grid, block, 0, st, *p);
     else hipLaunchKernelGGL(bl_abundance_posterior_kernel<false>, grid, block, 0, st, *p);
     return (int)hipGetLastError();

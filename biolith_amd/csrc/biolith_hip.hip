@@ -298,6 +298,82 @@ extern "C" int bl_device_count(int *count)
     return BL_OK;
 }
 
+// ------------------------------------------------------------------ the per-draw entries ----
+// bl_predict, bl_predict_scores, bl_predict_counts, bl_site_posterior, bl_abundance_posterior and bl_path_posterior run one kernel over
+// (site, posterior draw).  What they share is stated once: the name of a handle's model, the checks in front, the rows that go up on
+// first use, and the driver that takes the draws through the kernel in chunks.
+
+// The handle's model as the Python layer names it -- the one spelling every refusal uses.
+static const char *model_name(const bl_dataset *ds)
+{
+    static const char *const plain[] = {"occu", "occu_rn", "occu_fp (occu with false positives)", "occu_cop", "nmixture"};
+    static const char *const re_kind[] = {"occu_re (occu with random effects)", "occu_cs", "occu_re (occu with random effects)", "nmixture",
+                                          "occu_rn", "occu_rn", "occu_cop", "occu_cop", "occu_comb"};
+    if (ds->nsp > 1) return "a joint-species handle (it samples; use one handle per species)";
+    if (ds->model >= 0 && ds->model <= 4) return plain[ds->model];
+    if (ds->model == 6 && ds->re.kind >= 0 && ds->re.kind <= 8) return re_kind[ds->re.kind];
+    return ds->model == 8 ? "occu_dyn" : "this model";
+}
+// model 6 with one of these re.kind values
+static bool re_kind_in(const bl_dataset *ds, std::initializer_list<int> kinds)
+{
+    return ds->model == 6 && std::find(kinds.begin(), kinds.end(), ds->re.kind) != kinds.end();
+}
+
+// What every per-draw entry checks before it touches the device.  `serves`: does the entry serve this handle; `built`: what it does serve.
+static int per_draw_front(const char *entry, const bl_dataset *ds, int n_draws, const float *draws, bool any_output,
+                          bool (*serves)(const bl_dataset *), const char *built)
+{
+    if (!ds || !draws || n_draws <= 0 || !any_output) return bl_fail(BL_ERR_INVALID, "%s: bad argument", entry);
+    if (!serves(ds)) return bl_fail(BL_ERR_UNSUPPORTED, "%s: not built for %s (%s)", entry, model_name(ds), built);
+    if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
+    return set_device(ds);
+}
+
+// Rows that only a post-fit kernel reads (the raw observation covariates, occu_cop's durations) go up on first use and stay.
+static int upload_once(float **dev, const std::vector<float> &host)
+{
+    if (*dev) return BL_OK;
+    BL_HIP(hipMalloc((void **)dev, host.size() * 4));
+    BL_HIP(hipMemcpy(*dev, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    return BL_OK;
+}
+
+// One output of a per-draw entry, `bytes` per draw.  *dev receives the device buffer of a chunk of draws, or NULL where the output is
+// not wanted (host == NULL and not `always`) or empty; the kernel indexes it from the chunk's first draw.
+struct DrawOut {
+    void *host;
+    size_t bytes;
+    void **dev;
+    bool always; // allocated also when the caller does not want it back (a kernel's workspace)
+};
+
+// Runs launch(d_draws, n0, n1, grid_y) over the draws [n0, n1) in chunks of at most 256 MB / chunk_bytes draws (chunk_bytes: the entry's
+// largest output of one draw), grid_y = min(n1 - n0, 1024) rows of draws, and copies every wanted output back to host + n0 * bytes.
+template <size_t K, class Launch>
+static int run_over_draws(const bl_dataset *ds, int n_draws, const float *draws, size_t chunk_bytes, const DrawOut (&outs)[K],
+                          Launch launch)
+{
+    DevScratch scratch;
+    float *d_draws = nullptr;
+    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * ds->D * 4));
+    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * ds->D * 4, hipMemcpyHostToDevice));
+    const size_t fit = ((size_t)256 << 20) / std::max<size_t>(1, chunk_bytes); // draws whose largest output fills 256 MB
+    const int chunk = (int)std::min<size_t>((size_t)n_draws, std::max<size_t>(1, fit));
+    for (const DrawOut &o : outs) {
+        *o.dev = nullptr;
+        if ((o.host || o.always) && o.bytes) BL_HIP(scratch.alloc(o.dev, (size_t)chunk * o.bytes));
+    }
+    for (int n0 = 0; n0 < n_draws; n0 += chunk) {
+        const int n1 = std::min(n0 + chunk, n_draws);
+        BL_HIP(launch(d_draws, n0, n1, std::min(n1 - n0, 1024)));
+        for (const DrawOut &o : outs)
+            if (o.host && *o.dev)
+                BL_HIP(hipMemcpy((char *)o.host + (size_t)n0 * o.bytes, *o.dev, (size_t)(n1 - n0) * o.bytes, hipMemcpyDeviceToHost));
+    }
+    return BL_OK;
+}
+
 // ------------------------------------------------------------------ posterior predictive ----
 // (the generator, one per (draw, period, site): pred_rng.hpp)
 // occu (occu.py:207-241 with obs=None):  z ~ Bernoulli(psi),  y_j ~ Bernoulli(z * p_j)
@@ -363,52 +439,26 @@ __global__ void bl_predict_kernel(const float *__restrict__ rows, const float *_
 
 extern "C" int bl_predict(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, uint8_t *latent, uint8_t *y)
 {
-    if (!ds || !draws || n_draws <= 0 || (!latent && !y)) return bl_fail(BL_ERR_INVALID, "bl_predict: bad argument");
-    if (ds->nsp > 1) return bl_fail(BL_ERR_UNSUPPORTED, "bl_predict: a joint-species handle samples; predict from one handle per species");
-    if (ds->model == 8) return bl_fail(BL_ERR_UNSUPPORTED, "bl_predict: not built for the dynamic occupancy model");
-    if (ds->model == 3 || ds->model == 4)
-        return bl_fail(BL_ERR_UNSUPPORTED, "bl_predict: the count models (occu_cop, nmixture) use bl_predict_counts");
-    if (ds->model == 6 && ds->re.kind == 1)
-        return bl_fail(BL_ERR_UNSUPPORTED, "bl_predict: not built for occu_cs (its observed site is a continuous score)");
-    if (ds->model == 6 && ds->re.kind == 8)
-        return bl_fail(BL_ERR_UNSUPPORTED, "bl_predict: not built for occu_comb");
-    if (ds->model == 6 && (ds->re.kind == 3 || ds->re.kind == 6 || ds->re.kind == 7))
-        return bl_fail(BL_ERR_UNSUPPORTED, "bl_predict: the count models' sampled sites are counts (bl_predict_counts)");
-    if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
-    int rc = set_device(ds);
-    if (rc) return rc;
+    int rc = per_draw_front("bl_predict", ds, n_draws, draws, latent || y,
+                            [](const bl_dataset *d) {
+                                return d->nsp == 1 && ((d->model >= 0 && d->model <= 2) || re_kind_in(d, {0, 2, 4, 5}));
+                            },
+                            "occu, occu_fp, occu_re and occu_rn; the count models use bl_predict_counts, occu_cs bl_predict_scores");
+    if (rc || (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
     const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates, D = ds->D;
-    float *d_draws = nullptr;
-    unsigned char *d_lat = nullptr, *d_y = nullptr;
-    DevScratch scratch;
-    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * D * 4));
-    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * D * 4, hipMemcpyHostToDevice));
-    const size_t per_draw = (size_t)T * N * (y ? (size_t)J : 1); // bytes of the larger output
-    int chunk = (int)((256u << 20) / (per_draw ? per_draw : 1));
-    if (chunk < 1) chunk = 1;
-    if (chunk > n_draws) chunk = n_draws;
-    if (latent) BL_HIP(scratch.alloc((void **)&d_lat, (size_t)chunk * T * N));
-    if (y) BL_HIP(scratch.alloc((void **)&d_y, (size_t)chunk * J * T * N));
-    if (!ds->d_wraw) {
-        BL_HIP(hipMalloc((void **)&ds->d_wraw, ds->h_wraw.size() * 4));
-        BL_HIP(hipMemcpy(ds->d_wraw, ds->h_wraw.data(), ds->h_wraw.size() * 4, hipMemcpyHostToDevice));
-    }
-    const dim3 block(256);
-    for (int n0 = 0; n0 < n_draws; n0 += chunk) {
-        const int n1 = (n0 + chunk < n_draws) ? n0 + chunk : n_draws;
-        const dim3 grid((N + 255) / 256, (n1 - n0) < 1024 ? (n1 - n0) : 1024);
-        hipLaunchKernelGGL(bl_predict_kernel, grid, block, 0, nullptr, ds->d_rows, ds->d_wraw, ds->n_stride, N, T, J, ds->Ks, ds->Ko, D,
-                           d_draws, n0, n1, (unsigned long long)seed,
+    unsigned char *d_lat, *d_y;
+    const DrawOut outs[] = {{latent, (size_t)T * N, (void **)&d_lat, false}, {y, (size_t)J * T * N, (void **)&d_y, false}};
+    const size_t largest = (size_t)T * N * (y ? (size_t)J : 1); // bytes of the larger output of one draw
+    return run_over_draws(ds, n_draws, draws, largest, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
+        hipLaunchKernelGGL(bl_predict_kernel, dim3((N + 255) / 256, grid_y), dim3(256), 0, nullptr, ds->d_rows, ds->d_wraw, ds->n_stride,
+                           N, T, J, ds->Ks, ds->Ko, D, d_draws, n0, n1, (unsigned long long)seed,
                            // random-effects handles: Royle-Nichols (kind 4) / false positives (kind 2) run those branches with the effects
-                           ds->model == 6 && (ds->re.kind == 4 || ds->re.kind == 5) ? 1 : (ds->model == 6 && ds->re.kind == 2 ? 2 : ds->model),
-                           ds->max_abundance, ds->model == 6 && (ds->re.kind == 2 || ds->re.kind == 5) ? ds->re.fp_mode : ds->fp_mode, d_lat, d_y,
+                           re_kind_in(ds, {4, 5}) ? 1 : (re_kind_in(ds, {2}) ? 2 : ds->model),
+                           ds->max_abundance, re_kind_in(ds, {2, 5}) ? ds->re.fp_mode : ds->fp_mode, d_lat, d_y,
                            ds->model == 6 ? ds->re.o_u : -1, ds->model == 6 ? ds->re.o_v : -1, ds->model == 6 ? ds->re.o_e : -1,
-                           ds->model == 6 ? ((ds->re.kind == 2 || ds->re.kind == 5) ? ds->re.o_fp : -1) : D - 1);
-        BL_HIP(hipGetLastError());
-        if (latent) BL_HIP(hipMemcpy(latent + (size_t)n0 * T * N, d_lat, (size_t)(n1 - n0) * T * N, hipMemcpyDeviceToHost));
-        if (y) BL_HIP(hipMemcpy(y + (size_t)n0 * J * T * N, d_y, (size_t)(n1 - n0) * J * T * N, hipMemcpyDeviceToHost));
-    }
-    return BL_OK;
+                           ds->model == 6 ? (re_kind_in(ds, {2, 5}) ? ds->re.o_fp : -1) : D - 1);
+        return hipGetLastError();
+    });
 }
 
 // ---- conditional occupancy: P(z | data), the site-period log-likelihood and a draw of z, per posterior draw ----
@@ -416,21 +466,9 @@ extern "C" int bl_predict(bl_dataset *ds, int n_draws, const float *draws, uint6
 // density kernels read already carry y and the mask, so nothing is uploaded; a draw's layout is bl_predict's.
 extern "C" int bl_site_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *z_prob, uint8_t *z)
 {
-    if (!ds || !draws || n_draws <= 0 || (!log_lik && !z_prob && !z)) return bl_fail(BL_ERR_INVALID, "bl_site_posterior: bad argument");
-    if (ds->nsp > 1) return bl_fail(BL_ERR_UNSUPPORTED, "bl_site_posterior: a joint-species handle samples; use one handle per species");
-    const char *refused = nullptr;
-    if (ds->model == 1) refused = "occu_rn";
-    else if (ds->model == 3) refused = "occu_cop";
-    else if (ds->model == 4) refused = "nmixture";
-    else if (ds->model == 8) refused = "occu_dyn";
-    else if (ds->model == 6) {
-        const int k = ds->re.kind;
-        refused = k == 1 ? "occu_cs" : k == 3 ? "nmixture" : (k == 4 || k == 5) ? "occu_rn" : (k == 6 || k == 7) ? "occu_cop" : nullptr;
-    } else if (ds->model != 0 && ds->model != 2) refused = "this model";
-    if (refused)
-        return bl_fail(BL_ERR_UNSUPPORTED, "bl_site_posterior: not built for %s (occu, with or without false positives / random effects, and occu_comb)", refused);
-    if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
-    int rc = set_device(ds);
+    int rc = per_draw_front("bl_site_posterior", ds, n_draws, draws, log_lik || z_prob || z,
+                            [](const bl_dataset *d) { return d->nsp == 1 && (d->model == 0 || d->model == 2 || re_kind_in(d, {0, 2, 8})); },
+                            "occu, with or without false positives / random effects, and occu_comb");
     if (rc) return rc;
     const int N = ds->dims.n_sites, T = ds->dims.n_periods, D = ds->D;
     BlSitePostParams p{};
@@ -455,26 +493,14 @@ extern "C" int bl_site_posterior(bl_dataset *ds, int n_draws, const float *draws
             p.o_u = m.o_u; p.o_v = m.o_v; p.o_e = m.o_e;
         }
     }
-    float *d_draws = nullptr, *d_ll = nullptr, *d_q = nullptr;
-    unsigned char *d_z = nullptr;
-    DevScratch scratch;
-    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * D * 4));
-    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * D * 4, hipMemcpyHostToDevice));
     const size_t cells = (size_t)T * N; // per draw; the larger outputs are 4 bytes a cell
-    int chunk = (int)std::min<size_t>((size_t)n_draws, std::max<size_t>(1, ((size_t)256 << 20) / (cells * 4)));
-    if (log_lik) BL_HIP(scratch.alloc((void **)&d_ll, (size_t)chunk * cells * 4));
-    if (z_prob) BL_HIP(scratch.alloc((void **)&d_q, (size_t)chunk * cells * 4));
-    if (z) BL_HIP(scratch.alloc((void **)&d_z, (size_t)chunk * cells));
-    p.draws = d_draws; p.log_lik = d_ll; p.z_prob = d_q; p.z = d_z;
-    for (int n0 = 0; n0 < n_draws; n0 += chunk) {
-        const int n1 = (n0 + chunk < n_draws) ? n0 + chunk : n_draws;
-        p.n0 = n0; p.n1 = n1;
-        BL_HIP((hipError_t)bl_launch_site_posterior(&p, (n1 - n0) < 1024 ? (n1 - n0) : 1024, nullptr));
-        if (log_lik) BL_HIP(hipMemcpy(log_lik + (size_t)n0 * cells, d_ll, (size_t)(n1 - n0) * cells * 4, hipMemcpyDeviceToHost));
-        if (z_prob) BL_HIP(hipMemcpy(z_prob + (size_t)n0 * cells, d_q, (size_t)(n1 - n0) * cells * 4, hipMemcpyDeviceToHost));
-        if (z) BL_HIP(hipMemcpy(z + (size_t)n0 * cells, d_z, (size_t)(n1 - n0) * cells, hipMemcpyDeviceToHost));
-    }
-    return BL_OK;
+    const DrawOut outs[] = {{log_lik, cells * 4, (void **)&p.log_lik, false},
+                            {z_prob, cells * 4, (void **)&p.z_prob, false},
+                            {z, cells, (void **)&p.z, false}};
+    return run_over_draws(ds, n_draws, draws, cells * 4, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
+        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
+        return (hipError_t)bl_launch_site_posterior(&p, grid_y, nullptr);
+    });
 }
 
 // ---- conditional abundance: P(N | data), the site-period log-likelihood and a draw of N, per posterior draw ----
@@ -484,24 +510,9 @@ extern "C" int bl_site_posterior(bl_dataset *ds, int n_draws, const float *draws
 extern "C" int bl_abundance_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *n_mean,
                                       float *occ_prob, int32_t *n_draw)
 {
-    if (!ds || !draws || n_draws <= 0 || (!log_lik && !n_mean && !occ_prob && !n_draw))
-        return bl_fail(BL_ERR_INVALID, "bl_abundance_posterior: bad argument");
-    if (ds->nsp > 1) return bl_fail(BL_ERR_UNSUPPORTED, "bl_abundance_posterior: a joint-species handle samples; use one handle per species");
-    const char *refused = nullptr;
-    if (ds->model == 0) refused = "occu";
-    else if (ds->model == 2) refused = "occu with false positives";
-    else if (ds->model == 3) refused = "occu_cop";
-    else if (ds->model == 8) refused = "occu_dyn";
-    else if (ds->model == 6) {
-        const int k = ds->re.kind;
-        refused = (k == 0 || k == 2) ? "occu with random effects" : k == 1 ? "occu_cs" : (k == 6 || k == 7) ? "occu_cop" : k == 8 ? "occu_comb"
-                  : (k == 3 || k == 4 || k == 5) ? nullptr : "this model";
-    } else if (ds->model != 1 && ds->model != 4) refused = "this model";
-    if (refused)
-        return bl_fail(BL_ERR_UNSUPPORTED, "bl_abundance_posterior: not built for %s (occu_rn, with or without a false-positive rate / random effects, "
-                       "and nmixture, with or without random effects)", refused);
-    if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
-    int rc = set_device(ds);
+    int rc = per_draw_front("bl_abundance_posterior", ds, n_draws, draws, log_lik || n_mean || occ_prob || n_draw,
+                            [](const bl_dataset *d) { return d->nsp == 1 && (d->model == 1 || d->model == 4 || re_kind_in(d, {3, 4, 5})); },
+                            "occu_rn, with or without a false-positive rate / random effects, and nmixture, with or without random effects");
     if (rc) return rc;
     const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates, D = ds->D;
     BlAbundPostParams p{};
@@ -518,29 +529,15 @@ extern "C" int bl_abundance_posterior(bl_dataset *ds, int n_draws, const float *
         p.o_u = m.o_u; p.o_v = m.o_v; p.o_e = m.o_e;
     }
     if (p.K < 1 || p.K >= BL_RN_NB || (p.nmix && !p.tab)) return bl_fail(BL_ERR_INVALID, "bl_abundance_posterior: the handle carries no abundance table");
-    float *d_draws = nullptr, *d_ll = nullptr, *d_mean = nullptr, *d_occ = nullptr;
-    int *d_n = nullptr;
-    DevScratch scratch;
-    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * D * 4));
-    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * D * 4, hipMemcpyHostToDevice));
     const size_t cells = (size_t)T * N; // per draw; every output is 4 bytes a cell
-    int chunk = (int)std::min<size_t>((size_t)n_draws, std::max<size_t>(1, ((size_t)256 << 20) / (cells * 4)));
-    if (log_lik) BL_HIP(scratch.alloc((void **)&d_ll, (size_t)chunk * cells * 4));
-    if (n_mean) BL_HIP(scratch.alloc((void **)&d_mean, (size_t)chunk * cells * 4));
-    if (occ_prob) BL_HIP(scratch.alloc((void **)&d_occ, (size_t)chunk * cells * 4));
-    if (n_draw) BL_HIP(scratch.alloc((void **)&d_n, (size_t)chunk * cells * 4));
-    p.draws = d_draws; p.log_lik = d_ll; p.n_mean = d_mean; p.occ_prob = d_occ; p.n_draw = d_n;
-    for (int n0 = 0; n0 < n_draws; n0 += chunk) {
-        const int n1 = (n0 + chunk < n_draws) ? n0 + chunk : n_draws;
-        p.n0 = n0; p.n1 = n1;
-        BL_HIP((hipError_t)bl_launch_abundance_posterior(&p, (n1 - n0) < 1024 ? (n1 - n0) : 1024, nullptr));
-        const size_t off = (size_t)n0 * cells, bytes = (size_t)(n1 - n0) * cells * 4;
-        if (log_lik) BL_HIP(hipMemcpy(log_lik + off, d_ll, bytes, hipMemcpyDeviceToHost));
-        if (n_mean) BL_HIP(hipMemcpy(n_mean + off, d_mean, bytes, hipMemcpyDeviceToHost));
-        if (occ_prob) BL_HIP(hipMemcpy(occ_prob + off, d_occ, bytes, hipMemcpyDeviceToHost));
-        if (n_draw) BL_HIP(hipMemcpy(n_draw + off, d_n, bytes, hipMemcpyDeviceToHost));
-    }
-    return BL_OK;
+    const DrawOut outs[] = {{log_lik, cells * 4, (void **)&p.log_lik, false},
+                            {n_mean, cells * 4, (void **)&p.n_mean, false},
+                            {occ_prob, cells * 4, (void **)&p.occ_prob, false},
+                            {n_draw, cells * 4, (void **)&p.n_draw, false}};
+    return run_over_draws(ds, n_draws, draws, cells * 4, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
+        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
+        return (hipError_t)bl_launch_abundance_posterior(&p, grid_y, nullptr);
+    });
 }
 
 // ---- conditional dynamics: the smoothed P(z_t | all seasons' data), the transitions' pairwise terms, the site log-likelihood and a
@@ -551,56 +548,24 @@ extern "C" int bl_abundance_posterior(bl_dataset *ds, int n_draws, const float *
 extern "C" int bl_path_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *z_prob,
                                  float *col_prob, float *ext_prob, uint8_t *z)
 {
-    if (!ds || !draws || n_draws <= 0 || (!log_lik && !z_prob && !col_prob && !ext_prob && !z))
-        return bl_fail(BL_ERR_INVALID, "bl_path_posterior: bad argument");
-    if (ds->nsp > 1)
-        return bl_fail(BL_ERR_UNSUPPORTED, "bl_path_posterior: a joint-species handle samples and is not occu_dyn; use bl_site_posterior on one handle per species");
-    const char *refused = nullptr;
-    if (ds->model == 0) refused = "occu";
-    else if (ds->model == 1) refused = "occu_rn";
-    else if (ds->model == 2) refused = "occu_fp (occu with false positives)";
-    else if (ds->model == 3) refused = "occu_cop";
-    else if (ds->model == 4) refused = "nmixture";
-    else if (ds->model == 6) {
-        const int k = ds->re.kind;
-        refused = (k == 0 || k == 2) ? "occu_re (occu with random effects)" : k == 1 ? "occu_cs" : k == 3 ? "nmixture" : (k == 4 || k == 5) ? "occu_rn"
-                  : (k == 6 || k == 7) ? "occu_cop" : k == 8 ? "occu_comb" : "this model";
-    } else if (ds->model != 8) refused = "this model";
-    if (refused)
-        return bl_fail(BL_ERR_UNSUPPORTED, "bl_path_posterior: not built for %s (occu_dyn only; the static models' conditionals are "
-                       "bl_site_posterior / bl_abundance_posterior)", refused);
-    if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
-    int rc = set_device(ds);
+    int rc = per_draw_front("bl_path_posterior", ds, n_draws, draws, log_lik || z_prob || col_prob || ext_prob || z,
+                            [](const bl_dataset *d) { return d->model == 8; },
+                            "occu_dyn only; the static models' conditionals are bl_site_posterior / bl_abundance_posterior");
     if (rc) return rc;
     const int N = ds->dims.n_sites, T = ds->dims.n_periods, D = ds->D;
     BlPathPostParams p{};
     p.rows = ds->d_rows; p.ns = ds->n_stride; p.N = N; p.T = T; p.J = ds->dims.n_replicates; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = D;
     p.r0 = ds->KS; p.vw = ds->KO + 1; p.seed = (unsigned long long)seed;
-    float *d_draws = nullptr, *d_ll = nullptr, *d_q = nullptr, *d_col = nullptr, *d_ext = nullptr;
-    unsigned char *d_z = nullptr;
-    DevScratch scratch;
-    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * D * 4));
-    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * D * 4, hipMemcpyHostToDevice));
     const size_t cells = (size_t)T * N, pairs = (size_t)(T - 1) * N; // per draw; the largest output is 4 bytes a cell
-    int chunk = (int)std::min<size_t>((size_t)n_draws, std::max<size_t>(1, ((size_t)256 << 20) / (cells * 4)));
-    if (log_lik) BL_HIP(scratch.alloc((void **)&d_ll, (size_t)chunk * N * 4));
-    BL_HIP(scratch.alloc((void **)&d_q, (size_t)chunk * cells * 4));
-    if (col_prob && pairs) BL_HIP(scratch.alloc((void **)&d_col, (size_t)chunk * pairs * 4));
-    if (ext_prob && pairs) BL_HIP(scratch.alloc((void **)&d_ext, (size_t)chunk * pairs * 4));
-    if (z) BL_HIP(scratch.alloc((void **)&d_z, (size_t)chunk * cells));
-    p.draws = d_draws; p.log_lik = d_ll; p.z_prob = d_q; p.col_prob = d_col; p.ext_prob = d_ext; p.z = d_z;
-    for (int n0 = 0; n0 < n_draws; n0 += chunk) {
-        const int n1 = (n0 + chunk < n_draws) ? n0 + chunk : n_draws;
-        const size_t m = (size_t)(n1 - n0);
-        p.n0 = n0; p.n1 = n1;
-        BL_HIP((hipError_t)bl_launch_path_posterior(&p, (n1 - n0) < 1024 ? (n1 - n0) : 1024, nullptr));
-        if (log_lik) BL_HIP(hipMemcpy(log_lik + (size_t)n0 * N, d_ll, m * N * 4, hipMemcpyDeviceToHost));
-        if (z_prob) BL_HIP(hipMemcpy(z_prob + (size_t)n0 * cells, d_q, m * cells * 4, hipMemcpyDeviceToHost));
-        if (d_col) BL_HIP(hipMemcpy(col_prob + (size_t)n0 * pairs, d_col, m * pairs * 4, hipMemcpyDeviceToHost));
-        if (d_ext) BL_HIP(hipMemcpy(ext_prob + (size_t)n0 * pairs, d_ext, m * pairs * 4, hipMemcpyDeviceToHost));
-        if (z) BL_HIP(hipMemcpy(z + (size_t)n0 * cells, d_z, m * cells, hipMemcpyDeviceToHost));
-    }
-    return BL_OK;
+    const DrawOut outs[] = {{log_lik, (size_t)N * 4, (void **)&p.log_lik, false},
+                            {z_prob, cells * 4, (void **)&p.z_prob, true},        // (the kernel's workspace)
+                            {col_prob, pairs * 4, (void **)&p.col_prob, false},   // (T = 1: empty, skipped)
+                            {ext_prob, pairs * 4, (void **)&p.ext_prob, false},
+                            {z, cells, (void **)&p.z, false}};
+    return run_over_draws(ds, n_draws, draws, cells * 4, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
+        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
+        return (hipError_t)bl_launch_path_posterior(&p, grid_y, nullptr);
+    });
 }
 
 // ---- predictive scores of the continuous-score model (occu_cs.py:196-232 with obs=None) ----
@@ -641,40 +606,21 @@ __global__ void bl_predict_scores_kernel(const float *__restrict__ rows, const f
 
 extern "C" int bl_predict_scores(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, uint8_t *latent, uint8_t *f, float *s)
 {
-    if (!ds || !draws || n_draws <= 0 || (!latent && !f && !s)) return bl_fail(BL_ERR_INVALID, "bl_predict_scores: bad argument");
-    if (!(ds->model == 6 && ds->re.kind == 1)) return bl_fail(BL_ERR_UNSUPPORTED, "bl_predict_scores: an occu_cs dataset is required");
-    if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
-    int rc = set_device(ds);
-    if (rc) return rc;
+    int rc = per_draw_front("bl_predict_scores", ds, n_draws, draws, latent || f || s,
+                            [](const bl_dataset *d) { return re_kind_in(d, {1}); }, "an occu_cs dataset is required");
+    if (rc || (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
     const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates, D = ds->D;
-    float *d_draws = nullptr, *d_s = nullptr;
-    unsigned char *d_lat = nullptr, *d_f = nullptr;
-    DevScratch scratch;
-    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * D * 4));
-    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * D * 4, hipMemcpyHostToDevice));
-    const size_t per_draw = (size_t)T * N * J * 4;
-    int chunk = (int)((256u << 20) / (per_draw ? per_draw : 1));
-    if (chunk < 1) chunk = 1;
-    if (chunk > n_draws) chunk = n_draws;
-    if (latent) BL_HIP(scratch.alloc((void **)&d_lat, (size_t)chunk * T * N));
-    if (f) BL_HIP(scratch.alloc((void **)&d_f, (size_t)chunk * J * T * N));
-    if (s) BL_HIP(scratch.alloc((void **)&d_s, (size_t)chunk * J * T * N * 4));
-    if (!ds->d_wraw) {
-        BL_HIP(hipMalloc((void **)&ds->d_wraw, ds->h_wraw.size() * 4));
-        BL_HIP(hipMemcpy(ds->d_wraw, ds->h_wraw.data(), ds->h_wraw.size() * 4, hipMemcpyHostToDevice));
-    }
-    const dim3 block(256);
-    for (int n0 = 0; n0 < n_draws; n0 += chunk) {
-        const int n1 = (n0 + chunk < n_draws) ? n0 + chunk : n_draws;
-        const dim3 grid((N + 255) / 256, (n1 - n0) < 1024 ? (n1 - n0) : 1024);
-        hipLaunchKernelGGL(bl_predict_scores_kernel, grid, block, 0, nullptr, ds->d_rows, ds->d_wraw, ds->n_stride, N, T, J, ds->Ks, ds->Ko, D,
-                           d_draws, n0, n1, (unsigned long long)seed, d_lat, d_f, d_s);
-        BL_HIP(hipGetLastError());
-        if (latent) BL_HIP(hipMemcpy(latent + (size_t)n0 * T * N, d_lat, (size_t)(n1 - n0) * T * N, hipMemcpyDeviceToHost));
-        if (f) BL_HIP(hipMemcpy(f + (size_t)n0 * J * T * N, d_f, (size_t)(n1 - n0) * J * T * N, hipMemcpyDeviceToHost));
-        if (s) BL_HIP(hipMemcpy(s + (size_t)n0 * J * T * N, d_s, (size_t)(n1 - n0) * J * T * N * 4, hipMemcpyDeviceToHost));
-    }
-    return BL_OK;
+    unsigned char *d_lat, *d_f;
+    float *d_s;
+    const size_t visits = (size_t)J * T * N; // per draw
+    const DrawOut outs[] = {{latent, (size_t)T * N, (void **)&d_lat, false},
+                            {f, visits, (void **)&d_f, false},
+                            {s, visits * 4, (void **)&d_s, false}};
+    return run_over_draws(ds, n_draws, draws, visits * 4, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
+        hipLaunchKernelGGL(bl_predict_scores_kernel, dim3((N + 255) / 256, grid_y), dim3(256), 0, nullptr, ds->d_rows, ds->d_wraw,
+                           ds->n_stride, N, T, J, ds->Ks, ds->Ko, D, d_draws, n0, n1, (unsigned long long)seed, d_lat, d_f, d_s);
+        return hipGetLastError();
+    });
 }
 
 // ---- predictive counts of the count models (occu_cop, nmixture) ----
@@ -766,47 +712,25 @@ __global__ void bl_predict_counts_kernel(const float *__restrict__ rows, const f
 
 extern "C" int bl_predict_counts(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, int32_t *latent, int32_t *y)
 {
-    if (!ds || !draws || n_draws <= 0 || (!latent && !y)) return bl_fail(BL_ERR_INVALID, "bl_predict_counts: bad argument");
-    const bool nmix_re = ds->model == 6 && ds->re.kind == 3; // the N-mixture model with random effects
-    const bool cop_re = ds->model == 6 && (ds->re.kind == 6 || ds->re.kind == 7); // occu_cop with random effects (and a false-positive rate: kind 7)
-    if (ds->model != 3 && ds->model != 4 && !nmix_re && !cop_re)
-        return bl_fail(BL_ERR_UNSUPPORTED, "bl_predict_counts: for the count models (occu_cop, nmixture); use bl_predict");
-    if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
-    int rc = set_device(ds);
-    if (rc) return rc;
+    int rc = per_draw_front("bl_predict_counts", ds, n_draws, draws, latent || y,
+                            [](const bl_dataset *d) { return d->model == 3 || d->model == 4 || re_kind_in(d, {3, 6, 7}); },
+                            "the count models occu_cop and nmixture; use bl_predict");
+    if (rc || (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
+    const bool nmix_re = re_kind_in(ds, {3});   // the N-mixture model with random effects
+    const bool cop_re = re_kind_in(ds, {6, 7}); // occu_cop with random effects (and a false-positive rate: kind 7)
+    if ((ds->model == 3 || cop_re) && (rc = upload_once(&ds->d_dur, ds->h_dur))) return rc;
     const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates, D = ds->D;
-    float *d_draws = nullptr;
-    int *d_lat = nullptr, *d_y = nullptr;
-    DevScratch scratch;
-    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * D * 4));
-    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * D * 4, hipMemcpyHostToDevice));
-    const size_t per_draw = (size_t)T * N * 4 * (y ? (size_t)J : 1);
-    int chunk = (int)((256u << 20) / (per_draw ? per_draw : 1));
-    if (chunk < 1) chunk = 1;
-    if (chunk > n_draws) chunk = n_draws;
-    if (latent) BL_HIP(scratch.alloc((void **)&d_lat, (size_t)chunk * T * N * 4));
-    if (y) BL_HIP(scratch.alloc((void **)&d_y, (size_t)chunk * J * T * N * 4));
-    if (!ds->d_wraw) {
-        BL_HIP(hipMalloc((void **)&ds->d_wraw, ds->h_wraw.size() * 4));
-        BL_HIP(hipMemcpy(ds->d_wraw, ds->h_wraw.data(), ds->h_wraw.size() * 4, hipMemcpyHostToDevice));
-    }
-    if ((ds->model == 3 || cop_re) && !ds->d_dur) {
-        BL_HIP(hipMalloc((void **)&ds->d_dur, ds->h_dur.size() * 4));
-        BL_HIP(hipMemcpy(ds->d_dur, ds->h_dur.data(), ds->h_dur.size() * 4, hipMemcpyHostToDevice));
-    }
-    const dim3 block(256);
-    for (int n0 = 0; n0 < n_draws; n0 += chunk) {
-        const int n1 = (n0 + chunk < n_draws) ? n0 + chunk : n_draws;
-        const dim3 grid((N + 255) / 256, (n1 - n0) < 1024 ? (n1 - n0) : 1024);
-        hipLaunchKernelGGL(bl_predict_counts_kernel, grid, block, 0, nullptr, ds->d_rows, ds->d_wraw, ds->d_dur, ds->n_stride, N, T, J,
-                           ds->Ks, ds->Ko, D, d_draws, n0, n1, (unsigned long long)seed, nmix_re ? 4 : (cop_re ? 3 : ds->model), ds->max_abundance, ds->fp_mode,
-                           d_lat, d_y, (nmix_re || cop_re) ? ds->re.o_u : -1, (nmix_re || cop_re) ? ds->re.o_v : -1, (nmix_re || cop_re) ? ds->re.o_e : -1,
-                           cop_re && ds->fp_mode ? ds->re.o_fp : D - 1);
-        BL_HIP(hipGetLastError());
-        if (latent) BL_HIP(hipMemcpy(latent + (size_t)n0 * T * N, d_lat, (size_t)(n1 - n0) * T * N * 4, hipMemcpyDeviceToHost));
-        if (y) BL_HIP(hipMemcpy(y + (size_t)n0 * J * T * N, d_y, (size_t)(n1 - n0) * J * T * N * 4, hipMemcpyDeviceToHost));
-    }
-    return BL_OK;
+    int *d_lat, *d_y;
+    const DrawOut outs[] = {{latent, (size_t)T * N * 4, (void **)&d_lat, false}, {y, (size_t)J * T * N * 4, (void **)&d_y, false}};
+    const size_t largest = (size_t)T * N * 4 * (y ? (size_t)J : 1); // bytes of the larger output of one draw
+    const bool re = nmix_re || cop_re;
+    return run_over_draws(ds, n_draws, draws, largest, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
+        hipLaunchKernelGGL(bl_predict_counts_kernel, dim3((N + 255) / 256, grid_y), dim3(256), 0, nullptr, ds->d_rows, ds->d_wraw, ds->d_dur,
+                           ds->n_stride, N, T, J, ds->Ks, ds->Ko, D, d_draws, n0, n1, (unsigned long long)seed,
+                           nmix_re ? 4 : (cop_re ? 3 : ds->model), ds->max_abundance, ds->fp_mode, d_lat, d_y,
+                           re ? ds->re.o_u : -1, re ? ds->re.o_v : -1, re ? ds->re.o_e : -1, cop_re && ds->fp_mode ? ds->re.o_fp : D - 1);
+        return hipGetLastError();
+    });
 }
 
 extern "C" int bl_rng_streams(uint64_t seed, int chain, int nstreams, uint32_t *out)
@@ -2388,10 +2312,7 @@ extern "C" int bl_deterministic(bl_dataset *ds, int n_draws, const float *draws,
     if (chunk < 1) chunk = 1;
     if (chunk > n_draws) chunk = n_draws;
     BL_HIP(scratch.alloc((void **)&d_out, (size_t)chunk * per_draw));
-    if (prob_detection && !ds->d_wraw) {
-        BL_HIP(hipMalloc((void **)&ds->d_wraw, ds->h_wraw.size() * 4));
-        BL_HIP(hipMemcpy(ds->d_wraw, ds->h_wraw.data(), ds->h_wraw.size() * 4, hipMemcpyHostToDevice));
-    }
+    if (prob_detection && (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
     const dim3 block(256);
     for (int n0 = 0; n0 < n_draws; n0 += chunk) {
         const int n1 = (n0 + chunk < n_draws) ? n0 + chunk : n_draws;

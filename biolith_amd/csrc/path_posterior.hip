@@ -20,36 +20,11 @@
 // run-time index exists and nothing goes to scratch.  No LDS.
 #include "path_posterior.hpp"
 
-#include "nuts_kernel.hpp"
+#include "posterior_math.hpp"
 #include "pred_rng.hpp"
 
 namespace {
 
-constexpr float PP_LOG_TINY = -87.33654475f, PP_TINY = 1.1754944e-38f;
-
-// log(1 + e) for 0 <= e <= 1, relative error of a few ulps also where e is small (site_posterior.hip: sp_log1p)
-__device__ __forceinline__ float pp_log1p(float e)
-{
-    const float op = 1.0f + e, d = op - 1.0f;
-    const float r = bl_log(op) * (e * bl_rcp(d));
-    return d == 0.0f ? e : r;
-}
-struct PpSum { // Kahan
-    float s = 0.0f, c = 0.0f;
-    __device__ __forceinline__ void add(float x)
-    {
-        const float y = x - c, t = s + y;
-        c = (t - s) - y;
-        s = t;
-    }
-};
-// f = sigmoid(x), g = sigmoid(-x)
-__device__ __forceinline__ void pp_sig(float x, float &f, float &g)
-{
-    const float e = bl_exp(-fabsf(x)), r = bl_rcp(1.0f + e);
-    f = (x > 0.0f ? 1.0f : e) * r;
-    g = (x > 0.0f ? e : 1.0f) * r;
-}
 // pa = a / (a + b), pb = b / (a + b) for a, b >= 0 from the ratio of the smaller to the larger
 __device__ __forceinline__ void pp_norm2(float a, float b, float &pa, float &pb)
 {
@@ -78,19 +53,19 @@ __global__ void bl_path_posterior_kernel(const BlPathPostParams p)
             e_eps = fmaf(x, th[2 * (Ks + 1) + k + 1], e_eps);
         }
         float gam, ngam, eps, neps;
-        pp_sig(e_gam, gam, ngam);
-        pp_sig(e_eps, eps, neps);
-        const float lop = pp_log1p(bl_exp(-fabsf(e_psi)));
+        post_sig(e_gam, gam, ngam);
+        post_sig(e_eps, eps, neps);
+        const float lop = post_log1p(bl_exp(-fabsf(e_psi)));
         float lpi = fminf(e_psi, 0.0f) - lop, l1m = fminf(-e_psi, 0.0f) - lop; // log pi_t, log(1 - pi_t)
         const size_t o_site = (size_t)(n - p.n0) * N + i;   // [n][N]
         const size_t o_cell = (size_t)(n - p.n0) * T * N + i; // [n][T][N], period 0
         const size_t o_pair = (size_t)(n - p.n0) * (T - 1) * N + i; // [n][T - 1][N], period 0
         float *__restrict__ dq = p.z_prob + o_cell;
         // ---- forward: the filter ----
-        PpSum ll;
+        PostSum ll;
         float d = 0.0f;
         for (int t = 0; t < T; t++) {
-            PpSum a1;
+            PostSum a1;
             a1.add(lpi);
             float nd = 0.0f, nobs = 0.0f;
             for (int j = 0; j < J; j++) {
@@ -99,25 +74,25 @@ __global__ void bl_path_posterior_kernel(const BlPathPostParams p)
                 if (c == 0.0f) continue; // masked
                 float u = c * al[0];
                 for (int k = 1; k <= Ko; k++) u = fmaf(rows[r + (size_t)k * ns], al[k], u);
-                a1.add(fminf(u, 0.0f) - pp_log1p(bl_exp(-fabsf(u)))); // log sigma(c u)
+                a1.add(fminf(u, 0.0f) - post_log1p(bl_exp(-fabsf(u)))); // log sigma(c u)
                 nobs += 1.0f;
                 if (c > 0.0f) nd += 1.0f;
             }
-            const float A = a1.s, B = fmaf(nd, PP_LOG_TINY, l1m);
+            const float A = a1.s, B = fmaf(nd, POST_LOG_TINY, l1m);
             d = A - B;
-            if (nobs > 0.0f) ll.add(fmaxf(A, B) + pp_log1p(bl_exp(-fabsf(d)))); // (nothing observed: the season's likelihood is 1)
+            if (nobs > 0.0f) ll.add(fmaxf(A, B) + post_log1p(bl_exp(-fabsf(d)))); // (nothing observed: the season's likelihood is 1)
             dq[(size_t)t * N] = d;
             if (t + 1 < T) {
                 float f, g;
-                pp_sig(d, f, g);
-                lpi = bl_log(fmaxf(fmaf(f, neps, g * gam), PP_TINY));
-                l1m = bl_log(fmaxf(fmaf(f, eps, g * ngam), PP_TINY));
+                post_sig(d, f, g);
+                lpi = bl_log(fmaxf(fmaf(f, neps, g * gam), POST_TINY));
+                l1m = bl_log(fmaxf(fmaf(f, eps, g * ngam), POST_TINY));
             }
         }
         if (p.log_lik) p.log_lik[o_site] = ll.s;
         // ---- backward: the smoother, and the path drawn from its far end ----
         float rho, nrho;
-        pp_sig(d, rho, nrho);
+        post_sig(d, rho, nrho);
         bool zb = false;
         if (p.z) {
             BlPredRng rng(p.seed, ((unsigned long long)n * T + (T - 1)) * N + i);
@@ -126,7 +101,7 @@ __global__ void bl_path_posterior_kernel(const BlPathPostParams p)
         }
         for (int t = T - 2; t >= 0; t--) {
             float f, g, b1, nb1, b0, nb0;
-            pp_sig(dq[(size_t)t * N], f, g);
+            post_sig(dq[(size_t)t * N], f, g);
             pp_norm2(f * neps, g * gam, b1, nb1);
             pp_norm2(f * eps, g * ngam, b0, nb0);
             const float xi01 = rho * nb1, xi10 = nrho * b0;
@@ -147,8 +122,8 @@ __global__ void bl_path_posterior_kernel(const BlPathPostParams p)
 
 extern "C" int bl_launch_path_posterior(const BlPathPostParams *p, int grid_y, hipStream_t st)
 {
-    const int nt = p->N < 256 ? 64 : 256; // a small data set would idle three quarters of a 256-thread workgroup
-    const dim3 grid((p->N + nt - 1) / nt, grid_y), block(nt);
+    dim3 grid, block;
+    post_geometry(p->N, grid_y, grid, block);
     hipLaunchKernelGGL(bl_path_posterior_kernel, grid, block, 0, st, *p);
     return (int)hipGetLastError();
 }

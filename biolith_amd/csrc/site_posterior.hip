@@ -11,33 +11,17 @@
 // so that a cell's error stays a few ulps of its largest term however many visits it has.
 #include "site_posterior.hpp"
 
-#include "nuts_kernel.hpp"
+#include "posterior_math.hpp"
 #include "pred_rng.hpp"
 
 namespace {
 
-constexpr float SP_LOG_TINY = -87.33654475f, SP_TINY = 1.1754944e-38f, SP_LOG_EPS = -15.9423847f, SP_HL2PI = 0.9189385f;
+constexpr float SP_HL2PI = 0.9189385f;
 
-// log(1 + e) for 0 <= e <= 1, relative error of a few ulps also where e is small (log(op) e / (op - 1): the rounding of 1 + e cancels)
-__device__ __forceinline__ float sp_log1p(float e)
-{
-    const float op = 1.0f + e, d = op - 1.0f;
-    const float r = bl_log(op) * (e * bl_rcp(d));
-    return d == 0.0f ? e : r;
-}
-struct SpSum { // Kahan
-    float s = 0.0f, c = 0.0f;
-    __device__ __forceinline__ void add(float x)
-    {
-        const float y = x - c, t = s + y;
-        c = (t - s) - y;
-        s = t;
-    }
-};
 // f = sigmoid(phi): f, 1 - f, log f, log(1 - f)
 __device__ __forceinline__ void sp_rate(float phi, float &f, float &g, float &lf, float &l1f)
 {
-    const float e = bl_exp(-fabsf(phi)), l = sp_log1p(e), r = bl_rcp(1.0f + e);
+    const float e = bl_exp(-fabsf(phi)), l = post_log1p(e), r = bl_rcp(1.0f + e);
     f = (phi > 0.0f ? 1.0f : e) * r;
     g = (phi > 0.0f ? e : 1.0f) * r;
     lf = fminf(phi, 0.0f) - l;
@@ -59,18 +43,18 @@ __global__ void bl_site_posterior_kernel(const BlSitePostParams p)
         for (int k = 0; k < p.Ks; k++) eta = fmaf(rows[(size_t)k * ns + i], th[k + 1], eta);
         if (p.o_u >= 0) eta += th[p.o_u + i];
         const float vi = p.o_v >= 0 ? th[p.o_v + i] : 0.0f;
-        const float ee = bl_exp(-fabsf(eta)), lop = sp_log1p(ee);
+        const float ee = bl_exp(-fabsf(eta)), lop = post_log1p(ee);
         const float log_psi = fminf(eta, 0.0f) - lop, log_1mpsi = fminf(-eta, 0.0f) - lop;
         const float psi = (eta > 0.0f ? 1.0f : ee) * bl_rcp(1.0f + ee);
         // the draw's scalars: what a detection / a non-detection of block a costs at z = 0, the rate that acts at z = 1
-        float f1 = 0.0f, l1f1 = 0.0f, z0_det = SP_LOG_TINY, z0_non = 0.0f;
+        float f1 = 0.0f, l1f1 = 0.0f, z0_det = POST_LOG_TINY, z0_non = 0.0f;
         float fc = 0.0f, lgc = 0.0f, lp0 = 0.0f, lq0 = 0.0f, mu0 = 0.0f, mu1 = 0.0f, c0 = 0.0f, c1 = 0.0f, is0 = 0.0f, is1 = 0.0f;
         if constexpr (COMB) {
             float gc, fu, gu, lfc, lfu, lgu;
             sp_rate(th[p.o_x], fc, gc, lfc, lgc);
             sp_rate(th[p.o_x + 1], fu, gu, lfu, lgu);
-            lp0 = bl_log(fmaxf(fmaf(fu, gc, fc), SP_TINY)); // p0 = 1 - (1 - fc)(1 - fu), clamped to [tiny, 1 - eps]
-            lq0 = fmaxf(lgc + lgu, SP_LOG_EPS);
+            lp0 = bl_log(fmaxf(fmaf(fu, gc, fc), POST_TINY)); // p0 = 1 - (1 - fc)(1 - fu), clamped to [tiny, 1 - eps]
+            lq0 = fmaxf(lgc + lgu, POST_LOG_EPS);
             mu0 = th[p.o_x + 2]; mu1 = mu0 + bl_exp(th[p.o_x + 3]);
             c0 = th[p.o_x + 4] + SP_HL2PI; c1 = th[p.o_x + 5] + SP_HL2PI;              // log sigma + log(2 pi) / 2
             is0 = bl_exp(-2.0f * th[p.o_x + 4]); is1 = bl_exp(-2.0f * th[p.o_x + 5]);  // 1 / sigma^2
@@ -80,7 +64,7 @@ __global__ void bl_site_posterior_kernel(const BlSitePostParams p)
             if (p.fp_mode == 1) { f1 = f; l1f1 = z0_non; }
         }
         for (int t = 0; t < T; t++) {
-            SpSum a1;
+            PostSum a1;
             a1.add(log_psi);
             float nd = 0.0f, nn = 0.0f; // unmasked detections / non-detections of block a
             const float *__restrict__ al = th + p.a.o_al;
@@ -96,7 +80,7 @@ __global__ void bl_site_posterior_kernel(const BlSitePostParams p)
                     if (p.o_e >= 0) re += th[(size_t)p.o_e + (size_t)i * T * p.a.J + v];
                     u = fmaf(c, re, u);
                 }
-                const float e = bl_exp(-fabsf(u)), lsu = fminf(u, 0.0f) - sp_log1p(e); // log sigma(u)
+                const float e = bl_exp(-fabsf(u)), lsu = fminf(u, 0.0f) - post_log1p(e); // log sigma(u)
                 if (c > 0.0f) {
                     nd += 1.0f;
                     if (f1 > 0.0f) { // log(p + f (1 - p))
@@ -128,7 +112,7 @@ __global__ void bl_site_posterior_kernel(const BlSitePostParams p)
                         a1.add(bl_log(fmaf(fc, (u > 0.0f ? e : 1.0f) * rop, (u > 0.0f ? 1.0f : e) * rop)));
                     } else {        // log(1 - p) + log(1 - fc)
                         an += 1.0f;
-                        a1.add(fminf(u, 0.0f) - sp_log1p(e));
+                        a1.add(fminf(u, 0.0f) - post_log1p(e));
                     }
                 }
                 a1.add(an * lgc);
@@ -143,7 +127,7 @@ __global__ void bl_site_posterior_kernel(const BlSitePostParams p)
             }
             const float A = a1.s;
             const float d = A - B, e = bl_exp(-fabsf(d));
-            float l = fmaxf(A, B) + sp_log1p(e);
+            float l = fmaxf(A, B) + post_log1p(e);
             float q = (d > 0.0f ? 1.0f : e) * bl_rcp(1.0f + e);
             if (nobs == 0.0f) { l = 0.0f; q = psi; } // nothing observed: the cell's likelihood is 1 and the conditional is the prior
             const size_t o = ((size_t)(n - p.n0) * T + t) * N + i;
@@ -159,8 +143,8 @@ __global__ void bl_site_posterior_kernel(const BlSitePostParams p)
 
 extern "C" int bl_launch_site_posterior(const BlSitePostParams *p, int grid_y, hipStream_t st)
 {
-    const int nt = p->N < 256 ? 64 : 256; // a small data set would idle three quarters of a 256-thread workgroup
-    const dim3 grid((p->N + nt - 1) / nt, grid_y), block(nt);
+    dim3 grid, block;
+    post_geometry(p->N, grid_y, grid, block);
     if (p->comb) hipLaunchKernelGGL(bl_site_posterior_kernel<true>, grid, block, 0, st, *p);
     else hipLaunchKernelGGL(bl_site_posterior_kernel<false>, grid, block, 0, st, *p);
     return (int)hipGetLastError();

@@ -83,6 +83,7 @@ class _PinnedPool:
 
 
 _PINNED = _PinnedPool()
+_CTYPE = {np.float32: C.c_float, np.uint8: C.c_uint8, np.int32: C.c_int32}   # the per-draw entries' output types
 
 
 @dataclass
@@ -466,39 +467,39 @@ class OccuDataset:
         _PINNED.kick(self._lib)
         return out_psi, out_pd
 
+    def _per_draw(self, fn, draws, seed, outs, pinned=True):
+        """Calls a per-draw entry ``fn(handle, n, draws, seed, *outputs)`` for draws (n, D).  ``outs`` lists (wanted, shape behind
+        the draw axis, dtype) per output; returns the arrays, ``None`` where not wanted.  With ``pinned`` the 4-byte outputs come from
+        ``_big_empty``; the byte-sized ones never do."""
+        d = self._draw_matrix(draws)
+        n = d.shape[0]
+        empty = lambda dt: self._big_empty if pinned and np.dtype(dt).itemsize == 4 else np.empty
+        arrays = tuple(empty(dt)((n,) + shape, dtype=dt) if want else None for want, shape, dt in outs)
+        if n:
+            ptrs = [None if a is None else a.ctypes.data_as(C.POINTER(_CTYPE[a.dtype.type])) for a in arrays]
+            _ffi.check(fn(self._h, n, _fp(d), C.c_uint64(int(seed) & (2 ** 64 - 1)), *ptrs))
+            if pinned:
+                _PINNED.kick(self._lib)
+        return arrays
 
     def predictive(self, draws, seed: int = 0, latent: bool = True, y: bool = True):
         """Posterior predictive draws of the discrete sites for draws (n, D): the latent state
         (``z`` for occu / occu_cop, ``N_i`` for occu_rn / nmixture) as (n, T, N) and ``y`` as (n, J, T, N); uint8, or
         int32 for the count models
         (biolith/utils/predict.py:66-92; occu.py:208-241; occu_rn.py:194-221)."""
-        d = self._draw_matrix(draws)
-        n = d.shape[0]
         counts = self.model in ("occu_cop", "nmixture")  # their sampled sites are counts: int32 (bl_predict_counts)
-        dt, ct = (np.int32, C.c_int32) if counts else (np.uint8, C.c_uint8)
-        out_l = np.empty((n, self.T, self.N), dtype=dt) if latent else None
-        out_y = np.empty((n, self.J, self.T, self.N), dtype=dt) if y else None
-        if n:
-            ptr = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(ct))
-            fn = self._lib.bl_predict_counts if counts else self._lib.bl_predict
-            _ffi.check(fn(self._h, n, _fp(d), C.c_uint64(int(seed) & (2 ** 64 - 1)), ptr(out_l), ptr(out_y)))
-        return out_l, out_y
+        dt = np.int32 if counts else np.uint8
+        return self._per_draw(self._lib.bl_predict_counts if counts else self._lib.bl_predict, draws, seed,
+                              [(latent, (self.T, self.N), dt), (y, (self.J, self.T, self.N), dt)], pinned=False)
 
     def site_posterior(self, draws, seed: int = 0, log_lik: bool = True, z_prob: bool = True, z: bool = True):
         """Conditional occupancy for draws (n, D), each output (n, T, N): ``log_lik`` float32, the z-marginalised log-likelihood of a
         (period, site)'s unmasked observations; ``z_prob`` float32 = P(z = 1 | those observations, theta); ``z`` uint8 ~
         Bernoulli(z_prob), a function of (seed, draw, period, site).  occu (false positives, random effects) and occu_comb handles
         (include/biolith_hip.h: bl_site_posterior); no counterpart in the reference."""
-        d = self._draw_matrix(draws)
-        n = d.shape[0]
-        out_l = self._big_empty((n, self.T, self.N)) if log_lik else None
-        out_q = self._big_empty((n, self.T, self.N)) if z_prob else None
-        out_z = np.empty((n, self.T, self.N), dtype=np.uint8) if z else None
-        if n:
-            u8 = None if out_z is None else out_z.ctypes.data_as(C.POINTER(C.c_uint8))
-            _ffi.check(self._lib.bl_site_posterior(self._h, n, _fp(d), C.c_uint64(int(seed) & (2 ** 64 - 1)), _fp(out_l), _fp(out_q), u8))
-            _PINNED.kick(self._lib)
-        return out_l, out_q, out_z
+        cell = (self.T, self.N)
+        return self._per_draw(self._lib.bl_site_posterior, draws, seed,
+                              [(log_lik, cell, np.float32), (z_prob, cell, np.float32), (z, cell, np.uint8)])
 
     def abundance_posterior(self, draws, seed: int = 0, log_lik: bool = True, n_mean: bool = True, occ_prob: bool = True, n_draw: bool = True):
         """Conditional abundance for draws (n, D), each output (n, T, N): ``log_lik`` float32, the N-marginalised log-likelihood of a
@@ -506,18 +507,9 @@ class OccuDataset:
         P(N > 0 | those observations, theta); ``n_draw`` int32, one draw of N given them, a function of (seed, draw, period, site).
         occu_rn (false-positive rate, random effects) and nmixture (random effects) handles (include/biolith_hip.h:
         bl_abundance_posterior); no counterpart in the reference."""
-        d = self._draw_matrix(draws)
-        n = d.shape[0]
-        shape = (n, self.T, self.N)
-        out_l = self._big_empty(shape) if log_lik else None
-        out_m = self._big_empty(shape) if n_mean else None
-        out_q = self._big_empty(shape) if occ_prob else None
-        out_n = self._big_empty(shape, np.int32) if n_draw else None
-        if n:
-            i32 = None if out_n is None else out_n.ctypes.data_as(C.POINTER(C.c_int32))
-            _ffi.check(self._lib.bl_abundance_posterior(self._h, n, _fp(d), C.c_uint64(int(seed) & (2 ** 64 - 1)), _fp(out_l), _fp(out_m), _fp(out_q), i32))
-            _PINNED.kick(self._lib)
-        return out_l, out_m, out_q, out_n
+        cell = (self.T, self.N)
+        return self._per_draw(self._lib.bl_abundance_posterior, draws, seed,
+                              [(log_lik, cell, np.float32), (n_mean, cell, np.float32), (occ_prob, cell, np.float32), (n_draw, cell, np.int32)])
 
     def path_posterior(self, draws, seed: int = 0, log_lik: bool = True, z_prob: bool = True, col_prob: bool = True, ext_prob: bool = True,
                        z: bool = True):
@@ -526,33 +518,18 @@ class OccuDataset:
         ``ext_prob`` (n, T - 1, N) float32 = P(z_t = 0, z_t+1 = 1 | .) / P(z_t = 1, z_t+1 = 0 | .); ``z`` (n, T, N) uint8, one joint
         draw of the path by forward filtering, backward sampling, a function of (seed, draw, period, site)
         (include/biolith_hip.h: bl_path_posterior); builder-defined like the model."""
-        d = self._draw_matrix(draws)
-        n = d.shape[0]
-        out_l = self._big_empty((n, self.N)) if log_lik else None
-        out_q = self._big_empty((n, self.T, self.N)) if z_prob else None
-        out_c = self._big_empty((n, self.T - 1, self.N)) if col_prob else None
-        out_e = self._big_empty((n, self.T - 1, self.N)) if ext_prob else None
-        out_z = np.empty((n, self.T, self.N), dtype=np.uint8) if z else None
-        if n:
-            u8 = None if out_z is None else out_z.ctypes.data_as(C.POINTER(C.c_uint8))
-            _ffi.check(self._lib.bl_path_posterior(self._h, n, _fp(d), C.c_uint64(int(seed) & (2 ** 64 - 1)), _fp(out_l), _fp(out_q), _fp(out_c),
-                                                   _fp(out_e), u8))
-            _PINNED.kick(self._lib)
-        return out_l, out_q, out_c, out_e, out_z
+        cell, pair = (self.T, self.N), (self.T - 1, self.N)
+        return self._per_draw(self._lib.bl_path_posterior, draws, seed,
+                              [(log_lik, (self.N,), np.float32), (z_prob, cell, np.float32), (col_prob, pair, np.float32),
+                               (ext_prob, pair, np.float32), (z, cell, np.uint8)])
 
 
 def _predictive_scores(self, draws, seed: int = 0):
     """occu_cs: posterior predictive ``z`` (n, T, N), ``f`` (n, J, T, N) as uint8 and the scores ``s`` (n, J, T, N) float32
     (biolith/models/occu_cs.py:196-232 with obs withheld)."""
-    d = self._draw_matrix(draws)
-    n = d.shape[0]
-    z = np.empty((n, self.T, self.N), dtype=np.uint8)
-    f = np.empty((n, self.J, self.T, self.N), dtype=np.uint8)
-    s = np.empty((n, self.J, self.T, self.N), dtype=np.float32)
-    if n:
-        u8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))
-        _ffi.check(self._lib.bl_predict_scores(self._h, n, _fp(d), C.c_uint64(int(seed) & (2 ** 64 - 1)), u8(z), u8(f), _fp(s)))
-    return z, f, s
+    visit = (self.J, self.T, self.N)
+    return self._per_draw(self._lib.bl_predict_scores, draws, seed,
+                          [(True, (self.T, self.N), np.uint8), (True, visit, np.uint8), (True, visit, np.float32)], pinned=False)
 
 
 OccuDataset.predictive_scores = _predictive_scores

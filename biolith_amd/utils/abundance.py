@@ -21,13 +21,8 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from .data import prepare_data, species_dataset
-from .latent import _unmasked
-from .layout import draws_from_sites, layout_for
+from ._conditional import plate_last, prepare
 from .mcmc import LazySamples
-from .misc import time_limit
-
-SERVED = ("occu_rn", "nmixture")
 
 
 def conditional_abundance(
@@ -66,44 +61,13 @@ def conditional_abundance(
     >>> results = fit(occu_rn, **data, num_samples=10, num_warmup=10, num_chains=1)
     >>> lat = conditional_abundance(occu_rn, results.mcmc, **data)
     """
-    name = getattr(model_fn, "__biolith_amd_model__", None) if callable(model_fn) else None
-    if name is None:
-        raise TypeError("conditional_abundance(): model_fn must be a biolith_amd model (biolith_amd.models.occu_rn / nmixture)")
-    if name not in SERVED:
-        hint = "; use conditional_occupancy" if name in ("occu", "occu_comb") else ""
-        raise NotImplementedError(f"conditional_abundance(): not built for {name} (built: occu_rn with or without a false-positive rate / "
-                                  f"random effects, and nmixture with or without random effects){hint}")
-    device = int(kwargs.pop("device", 0))
-    site_covs, obs_covs, obs, _, _, _ = prepare_data(site_covs, obs_covs, obs, None)
-    valid = {k: v for k, v in dict(site_covs=site_covs, obs_covs=obs_covs, obs=obs).items() if v is not None}
-    spec = model_fn(**valid, **kwargs)
-    posterior = mcmc.get_samples()
-    beta = np.asarray(posterior["beta"], dtype=np.float32)    # (n, S, Ks+1)
-    n_species = beta.shape[1]
-    if n_species != spec.obs.shape[0] or beta.shape[2] != spec.site_covs.shape[1] + 1:
-        raise ValueError("conditional_abundance(): the data differ from the fitted model's (species or site covariate count)")
-    if np.asarray(posterior["alpha"]).shape[2] != spec.obs_covs.shape[3] + 1:
-        raise ValueError("conditional_abundance(): covariate counts differ from the fitted model's coefficients")
+    c = prepare("conditional_abundance", "occu_rn with or without a false-positive rate / random effects, and nmixture with or without "
+                "random effects", ("occu", "occu_comb"), model_fn, mcmc, site_covs, obs_covs, obs, kwargs)
 
-    X = np.asarray(spec.site_covs, dtype=np.float32)
-    n_obs = _unmasked(spec.obs, spec.obs_covs, np.isnan(X).any(-1))
-    N, T, J, Ko = spec.obs_covs.shape
-    layout = layout_for(spec, N=N, T=T, J=J, Ks=X.shape[1], Ko=Ko)
+    def body(ds, draws, sp, seed):
+        lam = ds.deterministic(draws, psi=True, prob_detection=False)[0]
+        log_lik, n_mean, occ_prob, n_draw = ds.abundance_posterior(draws, seed=seed)
+        return lam, n_mean, occ_prob, n_draw, log_lik
 
-    lam, ll, mean, occ, draw = [], [], [], [], []
-    with time_limit(timeout):
-        for sp in range(n_species):
-            ds, draws = species_dataset(spec, sp, device), draws_from_sites(layout, posterior, sp)
-            lam.append(ds.deterministic(draws, psi=True, prob_detection=False)[0])
-            out = ds.abundance_posterior(draws, seed=(int(random_seed) + (sp << 32)) & (2 ** 64 - 1))
-            for acc, a in zip((ll, mean, occ, draw), out):
-                acc.append(a)
-            ds.close()
-    out = LazySamples()
-    out["abundance"] = np.stack(lam, axis=-1)                             # (n, T, N, S)
-    out["N_mean"] = np.stack(mean, axis=-1)
-    out["occ_prob"] = np.stack(occ, axis=-1)
-    out["N_i"] = np.stack(draw, axis=-1).astype(np.int32)
-    out["log_lik"] = np.stack(ll, axis=-1)
-    out["n_obs"] = np.ascontiguousarray(n_obs.transpose(2, 1, 0)).astype(np.int32)   # (S, N, T) -> (T, N, S)
-    return out
+    lam, n_mean, occ_prob, n_draw, log_lik = c.per_species(random_seed, timeout, body)   # (n, T, N, S)
+    return LazySamples(abundance=lam, N_mean=n_mean, occ_prob=occ_prob, N_i=n_draw.astype(np.int32), log_lik=log_lik, n_obs=plate_last(c.n_obs))

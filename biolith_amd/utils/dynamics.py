@@ -13,13 +13,8 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from .data import prepare_data, species_dataset
-from .latent import _unmasked
-from .layout import draws_from_sites, layout_for
+from ._conditional import plate_last, prepare
 from .mcmc import LazySamples
-from .misc import time_limit
-
-SERVED = ("occu_dyn",)
 
 
 def conditional_dynamics(
@@ -61,53 +56,20 @@ def conditional_dynamics(
     >>> results = fit(occu_dyn, **data, num_samples=10, num_warmup=10, num_chains=1)
     >>> lat = conditional_dynamics(occu_dyn, results.mcmc, **data)
     """
-    name = getattr(model_fn, "__biolith_amd_model__", None) if callable(model_fn) else None
-    if name is None:
-        raise TypeError("conditional_dynamics(): model_fn must be a biolith_amd model (biolith_amd.models.occu_dyn)")
-    if name not in SERVED:
-        hint = ("; use conditional_occupancy" if name in ("occu", "occu_comb") else
-                "; use conditional_abundance" if name in ("occu_rn", "nmixture") else "")
-        raise NotImplementedError(f"conditional_dynamics(): not built for {name} (built: occu_dyn, the one model with a latent trajectory){hint}")
-    device = int(kwargs.pop("device", 0))
-    site_covs, obs_covs, obs, _, _, _ = prepare_data(site_covs, obs_covs, obs, None)
-    valid = {k: v for k, v in dict(site_covs=site_covs, obs_covs=obs_covs, obs=obs).items() if v is not None}
-    spec = model_fn(**valid, **kwargs)
-    posterior = mcmc.get_samples()
-    coef = {k: np.asarray(posterior[k], dtype=np.float32) for k in ("beta", "beta_col", "beta_ext")}     # (n, S, Ks+1)
-    n, n_species = coef["beta"].shape[0], coef["beta"].shape[1]
-    if n_species != spec.obs.shape[0] or any(c.shape[2] != spec.site_covs.shape[1] + 1 for c in coef.values()):
-        raise ValueError("conditional_dynamics(): the data differ from the fitted model's (species or site covariate count)")
-    if np.asarray(posterior["alpha"]).shape[2] != spec.obs_covs.shape[3] + 1:
-        raise ValueError("conditional_dynamics(): covariate counts differ from the fitted model's coefficients")
-
-    X = np.asarray(spec.site_covs, dtype=np.float32)
-    n_obs_period = _unmasked(spec.obs, spec.obs_covs, np.isnan(X).any(-1))                                # (S, N, T)
-    N, T, J, Ko = spec.obs_covs.shape
-    layout = layout_for(spec, N=N, T=T, J=J, Ks=X.shape[1], Ko=Ko)
-    Xc = np.nan_to_num(X)
+    c = prepare("conditional_dynamics", "occu_dyn, the one model with a latent trajectory",
+                ("occu", "occu_comb", "occu_rn", "nmixture"), model_fn, mcmc, site_covs, obs_covs, obs, kwargs, coef=("beta", "beta_col", "beta_ext"))
+    Xc = np.nan_to_num(c.X)
 
     def site(block, sp):   # (n, N): the fit's own deterministic sites (utils/fit.py: _assemble_dyn)
         b = block[:, sp, :]
         return (1.0 / (1.0 + np.exp(-(b[:, :1] + b[:, 1:] @ Xc.T)))).astype(np.float32)
 
-    rates = {k: [] for k in coef}
-    ll, q, col, ext, z = [], [], [], [], []
-    with time_limit(timeout):
-        for sp in range(n_species):
-            ds, draws = species_dataset(spec, sp, device), draws_from_sites(layout, posterior, sp)
-            for k in coef:
-                rates[k].append(site(coef[k], sp))
-            out = ds.path_posterior(draws, seed=(int(random_seed) + (sp << 32)) & (2 ** 64 - 1))
-            for acc, a in zip((ll, q, col, ext, z), out):
-                acc.append(a)
-            ds.close()
-    out = LazySamples()
-    out["psi"], out["gamma"], out["epsilon"] = (np.stack(rates[k], axis=-1) for k in ("beta", "beta_col", "beta_ext"))   # (n, N, S)
-    out["z_prob"] = np.stack(q, axis=-1)                                  # (n, T, N, S)
-    out["z"] = np.stack(z, axis=-1).astype(np.int32)
-    out["col_prob"] = np.stack(col, axis=-1)                              # (n, T - 1, N, S)
-    out["ext_prob"] = np.stack(ext, axis=-1)
-    out["log_lik"] = np.stack(ll, axis=-1)                                # (n, N, S)
-    out["n_obs"] = np.ascontiguousarray(n_obs_period.sum(-1).T).astype(np.int32)                  # (S, N) -> (N, S)
-    out["n_obs_period"] = np.ascontiguousarray(n_obs_period.transpose(2, 1, 0)).astype(np.int32)  # (S, N, T) -> (T, N, S)
-    return out
+    def body(ds, draws, sp, seed):
+        log_lik, z_prob, col, ext, z = ds.path_posterior(draws, seed=seed)
+        return tuple(site(c.coef[k], sp) for k in ("beta", "beta_col", "beta_ext")) + (z_prob, z, col, ext, log_lik)
+
+    # rates (n, N, S); z_prob, z (n, T, N, S); the pairs (n, T - 1, N, S); log_lik (n, N, S)
+    psi, gamma, eps, z_prob, z, col, ext, log_lik = c.per_species(random_seed, timeout, body)
+    return LazySamples(psi=psi, gamma=gamma, epsilon=eps, z_prob=z_prob, z=z.astype(np.int32), col_prob=col, ext_prob=ext, log_lik=log_lik,
+                       n_obs=np.ascontiguousarray(c.n_obs.sum(-1).T).astype(np.int32),   # (S, N) -> (N, S)
+                       n_obs_period=plate_last(c.n_obs))
