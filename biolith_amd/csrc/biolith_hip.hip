@@ -23,6 +23,7 @@
 #include "site_posterior.hpp"
 #include "abundance_posterior.hpp"
 #include "path_posterior.hpp"
+#include "score_posterior.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -299,7 +300,8 @@ extern "C" int bl_device_count(int *count)
 }
 
 // ------------------------------------------------------------------ the per-draw entries ----
-// bl_predict, bl_predict_scores, bl_predict_counts, bl_site_posterior, bl_abundance_posterior and bl_path_posterior run one kernel over
+// bl_predict, bl_predict_scores, bl_predict_counts, bl_site_posterior, bl_abundance_posterior, bl_path_posterior and bl_score_posterior run
+// one kernel over
 // (site, posterior draw).  What they share is stated once: the name of a handle's model, the checks in front, the rows that go up on
 // first use, and the driver that takes the draws through the kernel in chunks.
 
@@ -565,6 +567,35 @@ extern "C" int bl_path_posterior(bl_dataset *ds, int n_draws, const float *draws
     return run_over_draws(ds, n_draws, draws, cells * 4, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
         p.draws = d_draws; p.n0 = n0; p.n1 = n1;
         return (hipError_t)bl_launch_path_posterior(&p, grid_y, nullptr);
+    });
+}
+
+// ---- conditional scores: P(z | data) and P(f_j | data) of the continuous-score model, the cell log-likelihood and a joint draw of
+// (z, f), per posterior draw ----
+// (BUILDER-DEFINED: the reference's predict withholds the scores.)  Kernel: score_posterior.hip.  It reads the handle's rows (site
+// covariates, the visits' masks), its score rows and the raw observation covariates bl_predict_scores already uses, which go up on
+// first use; a draw's layout is the sampler's.  The chunk of draws is sized by f_prob, the largest output, when a visit-level output is wanted.
+extern "C" int bl_score_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *z_prob, uint8_t *z,
+                                  float *f_prob, uint8_t *f)
+{
+    int rc = per_draw_front("bl_score_posterior", ds, n_draws, draws, log_lik || z_prob || z || f_prob || f,
+                            [](const bl_dataset *d) { return re_kind_in(d, {1}); },
+                            "occu_cs only; the other models' conditionals are bl_site_posterior / bl_abundance_posterior / bl_path_posterior");
+    if (rc || (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
+    const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates;
+    BlScorePostParams p{};
+    p.rows = ds->d_rows; p.wraw = ds->d_wraw; p.scores = ds->re.scores;
+    p.ns = ds->n_stride; p.N = N; p.T = T; p.J = J; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = ds->D;
+    p.r0 = ds->KS; p.vw = ds->KO + 1; p.seed = (unsigned long long)seed;
+    const size_t cells = (size_t)T * N, visits = (size_t)J * cells; // per draw
+    const DrawOut outs[] = {{log_lik, cells * 4, (void **)&p.log_lik, false},
+                            {z_prob, cells * 4, (void **)&p.z_prob, false},
+                            {z, cells, (void **)&p.z, false},
+                            {f_prob, visits * 4, (void **)&p.f_prob, false},
+                            {f, visits, (void **)&p.f, false}};
+    return run_over_draws(ds, n_draws, draws, (f_prob || f ? visits : cells) * 4, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
+        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
+        return (hipError_t)bl_launch_score_posterior(&p, grid_y, nullptr);
     });
 }
 

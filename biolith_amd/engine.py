@@ -523,6 +523,18 @@ class OccuDataset:
                               [(log_lik, (self.N,), np.float32), (z_prob, cell, np.float32), (col_prob, pair, np.float32),
                                (ext_prob, pair, np.float32), (z, cell, np.uint8)])
 
+    def score_posterior(self, draws, seed: int = 0, visits: bool = True):
+        """Conditional scores of an occu_cs handle for draws (n, D): ``log_lik`` (n, T, N) float32, the cell's log-likelihood with z and
+        every f summed out; ``z_prob`` (n, T, N) float32 = P(z = 1 | the cell's scores, theta); ``z`` (n, T, N) uint8 ~ Bernoulli(z_prob);
+        ``f_prob`` (n, J, T, N) float32 = P(f_j = 1 | the cell's scores, theta), whether recording j was a true positive; ``f``
+        (n, J, T, N) uint8, drawn jointly with ``z`` (``f <= z``).  ``z`` and ``f`` are functions of (seed, draw, period, site), and ``z``
+        is the same with and without ``visits``; ``visits=False`` skips the two replicate-level outputs (``None``)
+        (include/biolith_hip.h: bl_score_posterior); no counterpart in the reference."""
+        cell, visit = (self.T, self.N), (self.J, self.T, self.N)
+        return self._per_draw(self._lib.bl_score_posterior, draws, seed,
+                              [(True, cell, np.float32), (True, cell, np.float32), (True, cell, np.uint8),
+                               (visits, visit, np.float32), (visits, visit, np.uint8)])
+
 
 def _predictive_scores(self, draws, seed: int = 0):
     """occu_cs: posterior predictive ``z`` (n, T, N), ``f`` (n, J, T, N) as uint8 and the scores ``s`` (n, J, T, N) float32

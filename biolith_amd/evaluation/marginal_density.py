@@ -13,6 +13,9 @@ path draws.
 The result of :func:`biolith_amd.utils.conditional_abundance` (``occu_rn`` / ``nmixture``) is accepted too: its ``log_lik`` is the same
 kind of term with the abundance N summed out, its ``n_obs`` the same count, so an ``occu`` and an ``occu_rn`` fit of the same detections
 compare on the same cells.
+
+The result of :func:`biolith_amd.utils.conditional_scores` (``occu_cs``) is accepted too: same keys, same shapes, the cell's unmasked
+scores with z and every f summed out.  ``expected_true_positives`` reads its ``f_prob``.
 """
 from __future__ import annotations
 
@@ -54,6 +57,12 @@ def finite_sample_abundance(latent) -> np.ndarray:
     """(draws, T, S): the total of ``N_i`` over the sites in each conditional draw of a ``conditional_abundance`` result -- the
     finite-sample population size of the surveyed sites."""
     return np.asarray(latent["N_i"], dtype=np.float64).sum(axis=2)
+
+
+def expected_true_positives(latent) -> np.ndarray:
+    """(draws, T, N, S): the sum of ``f_prob`` over the visits of a ``conditional_scores`` result -- the posterior expected number of
+    true-positive recordings in each (period, site), per posterior draw."""
+    return np.asarray(latent["f_prob"], dtype=np.float64).sum(axis=1)
 
 
 def finite_sample_turnover(latent) -> Dict[str, np.ndarray]:

@@ -1,4 +1,4 @@
-"""What ``conditional_occupancy``, ``conditional_abundance`` and ``conditional_dynamics`` share: the checks of the model and of the
+"""What ``conditional_occupancy``, ``conditional_abundance``, ``conditional_dynamics`` and ``conditional_scores`` share: the checks of the model and of the
 posterior against the data, the unmasked-observation counts, the coordinate layout, and the loop over one device handle per species."""
 from __future__ import annotations
 
@@ -11,7 +11,7 @@ from .layout import Layout, draws_from_sites, layout_for
 from .misc import time_limit
 
 SERVED_BY = {"occu": "conditional_occupancy", "occu_comb": "conditional_occupancy", "occu_rn": "conditional_abundance",
-             "nmixture": "conditional_abundance", "occu_dyn": "conditional_dynamics"}
+             "nmixture": "conditional_abundance", "occu_dyn": "conditional_dynamics", "occu_cs": "conditional_scores"}
 
 
 def _unmasked(obs, covs, site_nan):

@@ -422,6 +422,29 @@ int bl_path_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t 
                       float *ext_prob, uint8_t *z);
 
 /*
+ * Conditional scores -- BUILDER-DEFINED, NO REFERENCE COUNTERPART (biolith/utils/predict.py withholds the scores, so the z and f of
+ * bl_predict_scores are drawn from the prior).  occu_cs has two enumerated layers: the site-period state z and, per recording j,
+ * f_j ~ Bernoulli(z p_j), whether the score s_j came from the true-positive Normal(mu1, sigma1) or the background Normal(mu0, sigma0).
+ * Per posterior draw [beta | alpha | mu0 | log(mu1 - mu0) | log sigma0 | log sigma1] and (period, site), over the cell's unmasked
+ * visits (score, observation covariates and site covariates all present), n0_j / n1_j = log Normal(s_j; mu0, sigma0) / (s_j; mu1, sigma1):
+ *   mix_j = logaddexp(log p_j + n1_j, log(1 - p_j) + n0_j) = log p(s_j | z = 1)
+ *   A = log psi + sum_j mix_j,   B = log(1 - psi) + sum_j n0_j                             (z = 0 forces every f_j = 0)
+ *   log_lik [n_draws][T][N]    = logaddexp(A, B):   sum over cells = the likelihood part of -U of bl_logp_grad
+ *   z_prob  [n_draws][T][N]    = exp(A - log_lik) = P(z = 1 | the cell's scores, theta)
+ *   f_prob  [n_draws][J][T][N] = z_prob r_j = P(f_j = 1 | the cell's scores, theta),  r_j = exp(log p_j + n1_j - mix_j) = P(f_j = 1 | z = 1, s_j);
+ *                                a masked visit has no score to condition on: r_j = p_j (NaN covariates read as 0, as the model reads them)
+ *   z       [n_draws][T][N], f [n_draws][J][T][N]   one JOINT draw: z ~ Bernoulli(z_prob), f_j = z Bernoulli(r_j), so f_j <= z; a function of
+ *                                (seed, draw, period, site) only -- the cell's generator is bl_site_posterior's, its first uniform draws z,
+ *                                the next J draw f_0 .. f_J-1 in order, so z is the same whether or not f is asked for
+ * log p, log(1 - p), log psi, log(1 - psi) are exact log-sigmoids (no probability clamp).  A cell with no unmasked visit has log_lik = 0
+ * exactly and z_prob = psi.  Host memory, NULL = skip (all five NULL: BL_ERR_INVALID).  Serves handles of bl_dataset_create_cs; every other
+ * handle: BL_ERR_UNSUPPORTED, the message names the model (bl_site_posterior, bl_abundance_posterior and bl_path_posterior in turn refuse
+ * occu_cs).  BL_ERR_BUSY while a NUTS launch is in flight on the handle.
+ */
+int bl_score_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *z_prob, uint8_t *z,
+                       float *f_prob, uint8_t *f);
+
+/*
  * Multi-GPU: chain-parallel sampling and the gather of the draws.
  *
  * The reference's only multi-device strategy is chain_method="parallel" (biolith/utils/fit.py:109-113: one chain per

@@ -1,5 +1,5 @@
-"""One SHA-256 per output array of every post-fit entry (bl_site_posterior, bl_abundance_posterior, bl_path_posterior, bl_predict,
-bl_predict_counts, bl_predict_scores) on a fixed list of small handles, fixed draws and seed 3: two builds that print the same listing
+"""One SHA-256 per output array of every post-fit entry (bl_site_posterior, bl_abundance_posterior, bl_path_posterior,
+bl_score_posterior, bl_predict, bl_predict_counts, bl_predict_scores) on a fixed list of small handles, fixed draws and seed 3: two builds that print the same listing
 compute the same bits.  70 sites = a 64-thread block and a partial one, 300 = a 256-thread block and a partial one; 2 periods x 3
 visits with missing visits; occu_dyn once with a single period (no transitions).  Every posterior entry is also called with each
 output alone.      python tools/posterior_digest.py > listing.txt"""
@@ -57,6 +57,8 @@ def main():
                     calls.append((f"{posterior} {o} alone", (o,), (only[i],)))
             if ds.model == "occu_cs":
                 calls.append(("predictive_scores", ("z", "f", "s"), ds.predictive_scores(th, seed=3)))
+                calls.append(("score_posterior", ("log_lik", "z_prob", "z", "f_prob", "f"), ds.score_posterior(th, seed=3)))
+                calls.append(("score_posterior cells alone", ("log_lik", "z_prob", "z"), ds.score_posterior(th, seed=3, visits=False)[:3]))
             elif ds.model not in ("occu_dyn", "occu_comb"):
                 calls.append(("predictive", ("latent", "y"), ds.predictive(th, seed=3)))
             for entry, outs, arrays in calls:
