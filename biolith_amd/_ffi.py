@@ -74,7 +74,7 @@ EXPORTS = (
     "bl_comm_rccl_version", "bl_comm_unique_id", "bl_comm_init_rank", "bl_comm_init_all", "bl_comm_info", "bl_comm_destroy",
     "bl_gather_draws", "bl_result_block_layout", "bl_gather_unpack", "bl_host_alloc", "bl_host_free",
     "bl_nuts_env_overrides", "bl_env_overrides", "bl_site_posterior", "bl_abundance_posterior", "bl_path_posterior",
-    "bl_score_posterior",
+    "bl_score_posterior", "bl_count_posterior",
 )
 
 _lib = None
@@ -156,6 +156,7 @@ def load():
         L.bl_abundance_posterior.argtypes = [vp, C.c_int, fp, C.c_uint64, fp, fp, fp, C.POINTER(C.c_int32)]
         L.bl_path_posterior.argtypes = [vp, C.c_int, fp, C.c_uint64, fp, fp, fp, fp, C.POINTER(C.c_uint8)]
         L.bl_score_posterior.argtypes = [vp, C.c_int, fp, C.c_uint64, fp, fp, C.POINTER(C.c_uint8), fp, C.POINTER(C.c_uint8)]
+        L.bl_count_posterior.argtypes = [vp, C.c_int, fp, C.c_uint64, fp, fp, C.POINTER(C.c_uint8), fp, C.POINTER(C.c_int32)]
         L.bl_rng_streams.argtypes = [C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
         L.bl_adaptation_schedule.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
         u8p = C.POINTER(C.c_uint8)

@@ -24,6 +24,7 @@
 #include "abundance_posterior.hpp"
 #include "path_posterior.hpp"
 #include "score_posterior.hpp"
+#include "count_posterior.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -207,6 +208,10 @@ struct bl_dataset {
     // occu_cop: raw session durations, site-fastest [V][n_stride], for the predictive counts (lazy upload)
     std::vector<float> h_dur;
     float *d_dur = nullptr;
+    // occu_cop: per cell, the sum over its unmasked visits of y log(dur) - lgamma(y + 1), site-fastest [T][n_stride], for
+    // bl_count_posterior (lazy upload)
+    std::vector<float> h_ccell;
+    float *d_ccell = nullptr;
     // ---- last NUTS launch ----
     bool in_flight = false, have_run = false;
     int C = 0, S = 0, W = 0, k = 0, nloc = 0, lds_ld = 0, lds_bytes = 0, staged = 0, nvp = 0, ncw = 0, lane_grp = 0;
@@ -300,9 +305,8 @@ extern "C" int bl_device_count(int *count)
 }
 
 // ------------------------------------------------------------------ the per-draw entries ----
-// bl_predict, bl_predict_scores, bl_predict_counts, bl_site_posterior, bl_abundance_posterior, bl_path_posterior and bl_score_posterior run
-// one kernel over
-// (site, posterior draw).  What they share is stated once: the name of a handle's model, the checks in front, the rows that go up on
+// bl_predict, bl_predict_scores, bl_predict_counts, bl_site_posterior, bl_abundance_posterior, bl_path_posterior, bl_score_posterior and
+// bl_count_posterior run one kernel over (site, posterior draw).  What they share is stated once: the name of a handle's model, the checks in front, the rows that go up on
 // first use, and the driver that takes the draws through the kernel in chunks.
 
 // The handle's model as the Python layer names it -- the one spelling every refusal uses.
@@ -332,7 +336,8 @@ static int per_draw_front(const char *entry, const bl_dataset *ds, int n_draws, 
     return set_device(ds);
 }
 
-// Rows that only a post-fit kernel reads (the raw observation covariates, occu_cop's durations) go up on first use and stay.
+// Rows that only a post-fit kernel reads (the raw observation covariates, occu_cop's durations and per-cell constants) go up on first
+// use and stay.
 static int upload_once(float **dev, const std::vector<float> &host)
 {
     if (*dev) return BL_OK;
@@ -599,6 +604,45 @@ extern "C" int bl_score_posterior(bl_dataset *ds, int n_draws, const float *draw
     });
 }
 
+// ---- conditional counts: P(z | data) of the count-detection model, the cell log-likelihood, and how many of a visit's counted
+// detections were real -- their mean and a joint draw of (z, true counts) -- per posterior draw ----
+// (BUILDER-DEFINED: the reference's predict withholds the counts.)  Kernel: count_posterior.hip.  It reads the rows the occu_cop samplers
+// read (site covariates, the visits' (y_m, d_m, w..), Ysum / Dsum) and one row of its own, the cells' parameter-free constants, which goes
+// up on first use; a draw's layout is the sampler's.  The chunk of draws is sized by true_mean, the largest output, when a visit-level
+// output is wanted.
+extern "C" int bl_count_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *z_prob, uint8_t *z,
+                                  float *true_mean, int32_t *true_count)
+{
+    int rc = per_draw_front("bl_count_posterior", ds, n_draws, draws, log_lik || z_prob || z || true_mean || true_count,
+                            [](const bl_dataset *d) { return d->nsp == 1 && (d->model == 3 || re_kind_in(d, {6, 7})); },
+                            "occu_cop only, with or without a false-positive rate / random effects; the other models' conditionals are "
+                            "bl_site_posterior / bl_abundance_posterior / bl_path_posterior / bl_score_posterior");
+    if (rc || (rc = upload_once(&ds->d_ccell, ds->h_ccell))) return rc;
+    const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates;
+    BlCountPostParams p{};
+    p.rows = ds->d_rows; p.ccell = ds->d_ccell;
+    p.ns = ds->n_stride; p.N = N; p.T = T; p.J = J; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = ds->D;
+    p.r0 = ds->KS; p.vw = ds->KO + 2; p.r_sum = ds->KS + T * J * p.vw; p.seed = (unsigned long long)seed;
+    p.fp_mode = ds->fp_mode;
+    p.o_fp = p.o_u = p.o_v = p.o_e = -1;
+    if (ds->model == 6) {
+        const BlReModel &m = ds->re;
+        p.o_fp = m.o_fp; p.o_u = m.o_u; p.o_v = m.o_v; p.o_e = m.o_e;
+    } else if (ds->fp_mode) {
+        p.o_fp = ds->D - 1; // the trailing coordinate
+    }
+    const size_t cells = (size_t)T * N, visits = (size_t)J * cells; // per draw
+    const DrawOut outs[] = {{log_lik, cells * 4, (void **)&p.log_lik, false},
+                            {z_prob, cells * 4, (void **)&p.z_prob, false},
+                            {z, cells, (void **)&p.z, false},
+                            {true_mean, visits * 4, (void **)&p.true_mean, false},
+                            {true_count, visits * 4, (void **)&p.true_count, false}};
+    return run_over_draws(ds, n_draws, draws, (true_mean || true_count ? visits : cells) * 4, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
+        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
+        return (hipError_t)bl_launch_count_posterior(&p, grid_y, nullptr);
+    });
+}
+
 // ---- predictive scores of the continuous-score model (occu_cs.py:196-232 with obs=None) ----
 // z ~ Bernoulli(psi);  f_j ~ Bernoulli(z p_j);  s_j ~ Normal(mu_f, sigma_f)   (draw = [beta, alpha, mu0, log(mu1 - mu0), log sigma0, log sigma1])
 __global__ void bl_predict_scores_kernel(const float *__restrict__ rows, const float *__restrict__ wraw, int n_stride, int N, int T, int J,
@@ -729,8 +773,7 @@ __global__ void bl_predict_counts_kernel(const float *__restrict__ rows, const f
                 if (o_e >= 0) nu += th[o_e + (size_t)i * T * J + v];
                 int cnt = 0;
                 if (model == 4) {
-                    const float p = 1.0f / (1.0f + __expf(-nu));
-                    for (int m = 0; m < zn; m++) cnt += rng.uniform() < p ? 1 : 0; // Binomial(N, p), N <= 127
+                    cnt = bl_binomial(rng, zn, 1.0f / (1.0f + __expf(-nu))); // Binomial(N, p), N <= 127 (pred_rng.hpp)
                 } else {
                     const double rate = (double)dur[(size_t)v * n_stride + i] * ((zn ? (double)__expf(nu) : (double)f_u) + (double)f_c);
                     cnt = bl_poisson(rng, rate);
@@ -910,6 +953,7 @@ static int dataset_create_impl(const ModelOpts &mo, const bl_dims *dims, const f
     std::vector<float> rows((size_t)n_rows * n_stride, 0.0f);
     ds->h_wraw.assign((size_t)V * (Ko > 0 ? Ko : 1) * n_stride, 0.0f);
     if (model == 3) ds->h_dur.assign((size_t)V * n_stride, 0.0f);
+    if (model == 3) ds->h_ccell.assign((size_t)T * n_stride, 0.0f);
     const double LN2 = 0.69314718055994530942, LOG_TINY = -87.33654475055310898657;
     const int row_wc = KS, row_ka = KS + V * vw, row_kb = row_ka + T;
     double cop_const = 0.0; // occu_cop: sum over unmasked visits of y log(dur) - lgamma(y + 1)
@@ -959,7 +1003,7 @@ static int dataset_create_impl(const ModelOpts &mo, const bl_dims *dims, const f
         }
         for (int t = 0; t < T && model == 3; t++) {
             // occu_cop.py:150-156,236-255: visit = (y_m, d_m, w_1..w_Ko), masked visits contribute nothing
-            double ysum = 0.0, dsum = 0.0;
+            double ysum = 0.0, dsum = 0.0, ccell = 0.0;
             for (int j = 0; j < J; j++) {
                 const int v = t * J + j;
                 const size_t o = ((size_t)i * T + t) * J + j;
@@ -980,8 +1024,10 @@ static int dataset_create_impl(const ModelOpts &mo, const bl_dims *dims, const f
                 rows[r0 * n_stride + i] = y;
                 rows[(r0 + 1) * n_stride + i] = dur;
                 ysum += y; dsum += dur;
-                cop_const += (y > 0.0f ? (double)y * std::log((double)dur) : 0.0) - std::lgamma((double)y + 1.0);
+                const double c = (y > 0.0f ? (double)y * std::log((double)dur) : 0.0) - std::lgamma((double)y + 1.0);
+                cop_const += c; ccell += c;
             }
+            ds->h_ccell[(size_t)t * n_stride + i] = (float)ccell;
             rows[(size_t)(row_ka + t) * n_stride + i] = (float)ysum;
             rows[(size_t)(row_kb + t) * n_stride + i] = (float)dsum;
         }
@@ -1083,6 +1129,7 @@ extern "C" int bl_dataset_destroy(bl_dataset *ds)
     if (ds->d_wraw) hipFree(ds->d_wraw);
     if (ds->d_tab) hipFree(ds->d_tab);
     if (ds->d_dur) hipFree(ds->d_dur);
+    if (ds->d_ccell) hipFree(ds->d_ccell);
     if (ds->d_run) hipFree(ds->d_run);
     if (ds->d_xchg) hipFree(ds->d_xchg);
     if (ds->d_restate) hipFree(ds->d_restate);

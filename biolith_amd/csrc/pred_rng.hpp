@@ -26,3 +26,11 @@ struct BlPredRng {
         return (float)(r >> 8) * 5.9604644775390625e-08f;
     }
 };
+// Binomial(n, p) as n Bernoulli trials, one uniform each: exact, and the number of uniforms is n whatever p is
+// (nmixture's predictive counts, n <= 127; occu_cop's true detections among a visit's count)
+__device__ inline int bl_binomial(BlPredRng &rng, int n, float p)
+{
+    int cnt = 0;
+    for (int m = 0; m < n; m++) cnt += rng.uniform() < p ? 1 : 0;
+    return cnt;
+}

@@ -535,6 +535,19 @@ class OccuDataset:
                               [(True, cell, np.float32), (True, cell, np.float32), (True, cell, np.uint8),
                                (visits, visit, np.float32), (visits, visit, np.uint8)])
 
+    def count_posterior(self, draws, seed: int = 0, visits: bool = True):
+        """Conditional counts of an occu_cop handle for draws (n, D): ``log_lik`` (n, T, N) float32, the cell's log-likelihood with z
+        summed out (the Poisson pmf's parameter-free part included); ``z_prob`` (n, T, N) float32 = P(z = 1 | the cell's counts, theta);
+        ``z`` (n, T, N) uint8 ~ Bernoulli(z_prob); ``true_mean`` (n, J, T, N) float32 = z_prob y_j rho_j, the expected number of visit
+        j's counted detections that were real, rho_j = lambda_j / (lambda_j + rate_fp_constant); ``true_count`` (n, J, T, N) int32 =
+        z Binomial(y_j, rho_j), drawn jointly with ``z`` (``true_count <= z y``).  ``z`` and ``true_count`` are functions of (seed, draw,
+        period, site), and ``z`` is the same with and without ``visits``; ``visits=False`` skips the two visit-level outputs (``None``)
+        (include/biolith_hip.h: bl_count_posterior); no counterpart in the reference."""
+        cell, visit = (self.T, self.N), (self.J, self.T, self.N)
+        return self._per_draw(self._lib.bl_count_posterior, draws, seed,
+                              [(True, cell, np.float32), (True, cell, np.float32), (True, cell, np.uint8),
+                               (visits, visit, np.float32), (visits, visit, np.int32)])
+
 
 def _predictive_scores(self, draws, seed: int = 0):
     """occu_cs: posterior predictive ``z`` (n, T, N), ``f`` (n, J, T, N) as uint8 and the scores ``s`` (n, J, T, N) float32

@@ -16,6 +16,11 @@ compare on the same cells.
 
 The result of :func:`biolith_amd.utils.conditional_scores` (``occu_cs``) is accepted too: same keys, same shapes, the cell's unmasked
 scores with z and every f summed out.  ``expected_true_positives`` reads its ``f_prob``.
+
+So is the result of :func:`biolith_amd.utils.conditional_counts` (``occu_cop``): ``lppd_marginal``, ``waic_marginal`` and
+``finite_sample_occupancy`` read its ``log_lik``, ``n_obs`` and ``z`` -- the cell's unmasked counts with z summed out, the Poisson
+pmf's parameter-free part included, so a count model is compared with an occu or occu_rn fit on the same cells only where the data
+are the same.  ``expected_true_detections`` reads its ``true_mean``.
 """
 from __future__ import annotations
 
@@ -63,6 +68,12 @@ def expected_true_positives(latent) -> np.ndarray:
     """(draws, T, N, S): the sum of ``f_prob`` over the visits of a ``conditional_scores`` result -- the posterior expected number of
     true-positive recordings in each (period, site), per posterior draw."""
     return np.asarray(latent["f_prob"], dtype=np.float64).sum(axis=1)
+
+
+def expected_true_detections(latent) -> np.ndarray:
+    """(draws, T, N, S): the sum of ``true_mean`` over the visits of a ``conditional_counts`` result -- the posterior expected number of
+    a (period, site)'s counted detections that were real rather than false positives, per posterior draw."""
+    return np.asarray(latent["true_mean"], dtype=np.float64).sum(axis=1)
 
 
 def finite_sample_turnover(latent) -> Dict[str, np.ndarray]:

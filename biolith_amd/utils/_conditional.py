@@ -1,5 +1,5 @@
-"""What ``conditional_occupancy``, ``conditional_abundance``, ``conditional_dynamics`` and ``conditional_scores`` share: the checks of the model and of the
-posterior against the data, the unmasked-observation counts, the coordinate layout, and the loop over one device handle per species."""
+"""What ``conditional_occupancy``, ``conditional_abundance``, ``conditional_dynamics``, ``conditional_scores`` and ``conditional_counts``
+share: the checks of the model and of the posterior against the data, the unmasked-observation counts, the coordinate layout, and the loop over one device handle per species."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -11,7 +11,8 @@ from .layout import Layout, draws_from_sites, layout_for
 from .misc import time_limit
 
 SERVED_BY = {"occu": "conditional_occupancy", "occu_comb": "conditional_occupancy", "occu_rn": "conditional_abundance",
-             "nmixture": "conditional_abundance", "occu_dyn": "conditional_dynamics", "occu_cs": "conditional_scores"}
+             "nmixture": "conditional_abundance", "occu_dyn": "conditional_dynamics", "occu_cs": "conditional_scores",
+             "occu_cop": "conditional_counts"}
 
 
 def _unmasked(obs, covs, site_nan):
@@ -48,10 +49,10 @@ class Conditional:
         return tuple(np.stack(a, axis=-1) for a in zip(*parts))
 
 
-def prepare(fn, built, hint_for, model_fn, mcmc, site_covs, obs_covs, obs, kwargs, coef=("beta",)) -> Conditional:
+def prepare(fn, built, hint_for, model_fn, mcmc, site_covs, obs_covs, obs, kwargs, coef=("beta",), session_duration=None) -> Conditional:
     """The front of ``fn`` (one of ``SERVED_BY``'s values): refuse what it does not serve (``built`` says what it does; a model in
     ``hint_for`` is pointed to the function that serves it), build the model's spec from the data as ``fit`` does, and check the
-    posterior's ``coef`` blocks and ``alpha`` against it."""
+    posterior's ``coef`` blocks and ``alpha`` against it.  ``session_duration`` (occu_cop) is normalised with the data and handed to the model."""
     served = [m for m, f in SERVED_BY.items() if f == fn]
     name = getattr(model_fn, "__biolith_amd_model__", None) if callable(model_fn) else None
     if name is None:
@@ -60,8 +61,8 @@ def prepare(fn, built, hint_for, model_fn, mcmc, site_covs, obs_covs, obs, kwarg
         hint = f"; use {SERVED_BY[name]}" if name in hint_for else ""
         raise NotImplementedError(f"{fn}(): not built for {name} (built: {built}){hint}")
     device = int(kwargs.pop("device", 0))
-    site_covs, obs_covs, obs, _, _, _ = prepare_data(site_covs, obs_covs, obs, None)
-    valid = {k: v for k, v in dict(site_covs=site_covs, obs_covs=obs_covs, obs=obs).items() if v is not None}
+    site_covs, obs_covs, obs, session_duration, _, _ = prepare_data(site_covs, obs_covs, obs, session_duration)
+    valid = {k: v for k, v in dict(site_covs=site_covs, obs_covs=obs_covs, obs=obs, session_duration=session_duration).items() if v is not None}
     spec = model_fn(**valid, **kwargs)
     posterior = mcmc.get_samples()
     blocks = {k: np.asarray(posterior[k], dtype=np.float32) for k in coef}     # (n, S, Ks+1)

@@ -62,7 +62,7 @@ def conditional_abundance(
     >>> lat = conditional_abundance(occu_rn, results.mcmc, **data)
     """
     c = prepare("conditional_abundance", "occu_rn with or without a false-positive rate / random effects, and nmixture with or without "
-                "random effects", ("occu", "occu_comb", "occu_cs"), model_fn, mcmc, site_covs, obs_covs, obs, kwargs)
+                "random effects", ("occu", "occu_comb", "occu_cs", "occu_cop"), model_fn, mcmc, site_covs, obs_covs, obs, kwargs)
 
     def body(ds, draws, sp, seed):
         lam = ds.deterministic(draws, psi=True, prob_detection=False)[0]

@@ -57,7 +57,7 @@ def conditional_dynamics(
     >>> lat = conditional_dynamics(occu_dyn, results.mcmc, **data)
     """
     c = prepare("conditional_dynamics", "occu_dyn, the one model with a latent trajectory",
-                ("occu", "occu_comb", "occu_rn", "nmixture", "occu_cs"), model_fn, mcmc, site_covs, obs_covs, obs, kwargs, coef=("beta", "beta_col", "beta_ext"))
+                ("occu", "occu_comb", "occu_rn", "nmixture", "occu_cs", "occu_cop"), model_fn, mcmc, site_covs, obs_covs, obs, kwargs, coef=("beta", "beta_col", "beta_ext"))
     Xc = np.nan_to_num(c.X)
 
     def site(block, sp):   # (n, N): the fit's own deterministic sites (utils/fit.py: _assemble_dyn)

@@ -53,7 +53,7 @@ def conditional_occupancy(
     >>> lat = conditional_occupancy(occu, results.mcmc, **data)
     """
     c = prepare("conditional_occupancy", "occu with or without false positives / random effects, and occu_comb",
-                ("occu_dyn", "occu_cs"), model_fn, mcmc, site_covs, obs_covs, obs, kwargs)
+                ("occu_dyn", "occu_cs", "occu_cop"), model_fn, mcmc, site_covs, obs_covs, obs, kwargs)
     comb, ex, n_obs = c.spec.model == "occu_comb", c.spec.extras, c.n_obs
     if comb:
         sc_ok = ~(np.isnan(ex["scores_obs"]) | c.site_nan[None, :, None, None])

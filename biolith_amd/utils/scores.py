@@ -63,7 +63,7 @@ def conditional_scores(
     >>> lat = conditional_scores(occu_cs, results.mcmc, **data)
     """
     c = prepare("conditional_scores", "occu_cs, the one model with a per-recording indicator",
-                ("occu", "occu_comb", "occu_rn", "nmixture", "occu_dyn"), model_fn, mcmc, site_covs, obs_covs, obs, kwargs)
+                ("occu", "occu_comb", "occu_rn", "nmixture", "occu_dyn", "occu_cop"), model_fn, mcmc, site_covs, obs_covs, obs, kwargs)
 
     def body(ds, draws, sp, seed):
         psi = ds.deterministic(draws, psi=True, prob_detection=False)[0]

@@ -445,6 +445,34 @@ int bl_score_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t
                        float *f_prob, uint8_t *f);
 
 /*
+ * Conditional counts -- BUILDER-DEFINED, NO REFERENCE COUNTERPART (biolith/utils/predict.py withholds the counts, so the z of
+ * bl_predict_counts is drawn from the prior: a site where the species was counted can come back unoccupied).  occu_cop
+ * (occu_cop.py:150-255): y_j ~ Poisson(d_j (z lambda_j + (1 - z) f_u + f_c)).  Per posterior draw [beta | alpha | (phi = log rate) |
+ * (log sds) | (effects)] and (period, site), over the cell's unmasked visits j (count, observation covariates and site covariates all
+ * present), with nu_j = alpha . (1, w_j) + site_re_det + obs_re_j where the handle has them, lambda_j = exp(min(nu_j, 80)) (the
+ * sampler's clamp), f the sampled rate (0 without one), f1 = f for BL_FP_CONSTANT else 0, f0 = f in either mode, and the
+ * parameter-free c_j = y_j log d_j - lgamma(y_j + 1):
+ *   A = log psi       + sum_j [ y_j log(lambda_j + f1) - d_j (lambda_j + f1) + c_j ]
+ *   B = log(1 - psi)  + sum_j [ y_j log f0 - d_j f0 + c_j ]      (f0 = 0: log(1 - psi) + sum c_j if the counts sum to 0, else -inf)
+ *   log_lik    [n_draws][T][N]    = logaddexp(A, B):   sum over cells = -U - log prior of bl_logp_grad (c_j included)
+ *   z_prob     [n_draws][T][N]    = sigmoid(A - B) = P(z = 1 | the cell's counts, theta)
+ *   true_mean  [n_draws][J][T][N] = z_prob y_j rho_j,  rho_j = lambda_j / (lambda_j + f1): given z = 1 the real detections among the y_j
+ *                                   counted ones are Binomial(y_j, rho_j) (Poisson thinning; rho_j = 1 unless BL_FP_CONSTANT), given z = 0 none
+ *   z          [n_draws][T][N], true_count [n_draws][J][T][N]   one JOINT draw: z ~ Bernoulli(z_prob), true_count_j = z Binomial(y_j, rho_j),
+ *                                   so true_count_j <= z y_j; a function of (seed, draw, period, site) only -- the cell's generator is
+ *                                   bl_site_posterior's, its first uniform draws z, the visits' follow in j order (how many depends on the
+ *                                   data only), so z is the same whether or not a visit-level output is asked for
+ * log psi and log(1 - psi) are exact log-sigmoids, with site_re_occ in the predictor where present.  A cell with no unmasked visit has
+ * log_lik = 0 exactly and z_prob = psi; without a rate a cell with a positive count has z_prob = 1 exactly and log_lik = A; a masked
+ * visit has no count: true_mean = true_count = 0.  Host memory, NULL = skip (all five NULL: BL_ERR_INVALID).  Serves one-species handles of
+ * bl_dataset_create_cop (with or without a rate) and bl_dataset_create_cop_re; every other handle: BL_ERR_UNSUPPORTED, the message names
+ * the model (bl_site_posterior, bl_abundance_posterior, bl_path_posterior and bl_score_posterior in turn refuse occu_cop).  BL_ERR_BUSY
+ * while a NUTS launch is in flight on the handle.
+ */
+int bl_count_posterior(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, float *log_lik, float *z_prob, uint8_t *z,
+                       float *true_mean, int32_t *true_count);
+
+/*
  * Multi-GPU: chain-parallel sampling and the gather of the draws.
  *
  * The reference's only multi-device strategy is chain_method="parallel" (biolith/utils/fit.py:109-113: one chain per
