@@ -25,6 +25,7 @@
 #include "path_posterior.hpp"
 #include "score_posterior.hpp"
 #include "count_posterior.hpp"
+#include "comb_predict.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -205,6 +206,10 @@ struct bl_dataset {
     // raw nan_to_num'd obs covariates, site-fastest [V][Ko][n_stride], for prob_detection (lazy upload)
     std::vector<float> h_wraw;
     float *d_wraw = nullptr;
+    // occu_comb: the same for the ARU block, [T Jaru][Karu][n_stride], for bl_predict_comb / bl_deterministic_comb (lazy upload; h_wraw
+    // holds the point counts', Kpc wide)
+    std::vector<float> h_araw;
+    float *d_araw = nullptr;
     // occu_cop: raw session durations, site-fastest [V][n_stride], for the predictive counts (lazy upload)
     std::vector<float> h_dur;
     float *d_dur = nullptr;
@@ -305,7 +310,7 @@ extern "C" int bl_device_count(int *count)
 }
 
 // ------------------------------------------------------------------ the per-draw entries ----
-// bl_predict, bl_predict_scores, bl_predict_counts, bl_site_posterior, bl_abundance_posterior, bl_path_posterior, bl_score_posterior and
+// bl_predict, bl_predict_scores, bl_predict_counts, bl_predict_comb, bl_deterministic_comb, bl_site_posterior, bl_abundance_posterior, bl_path_posterior, bl_score_posterior and
 // bl_count_posterior run one kernel over (site, posterior draw).  What they share is stated once: the name of a handle's model, the checks in front, the rows that go up on
 // first use, and the driver that takes the draws through the kernel in chunks.
 
@@ -695,6 +700,64 @@ extern "C" int bl_predict_scores(bl_dataset *ds, int n_draws, const float *draws
         hipLaunchKernelGGL(bl_predict_scores_kernel, dim3((N + 255) / 256, grid_y), dim3(256), 0, nullptr, ds->d_rows, ds->d_wraw,
                            ds->n_stride, N, T, J, ds->Ks, ds->Ko, D, d_draws, n0, n1, (unsigned long long)seed, d_lat, d_f, d_s);
         return hipGetLastError();
+    });
+}
+
+// ---- occu_comb: the posterior predictive of its three observed sites, and its deterministic sites ----
+// (bl_predict_comb is BUILDER-DEFINED: the reference's predict cannot withhold the scores from this model.)  Kernels: comb_predict.hip.
+// They read the site covariates from the head of the handle's rows and the two detection blocks' raw covariates, which go up on first
+// use (the density rows are folded by the observation); a draw's layout is the sampler's.  With no point counts the handle holds a
+// one-replicate stand-in: the block is empty here (cm.Jpc = 0).
+static bool serves_comb(const bl_dataset *d) { return re_kind_in(d, {8}); }
+static int comb_predict_params(bl_dataset *ds, BlCombPredParams &p)
+{
+    int rc = upload_once(&ds->d_wraw, ds->h_wraw);
+    if (rc || (rc = upload_once(&ds->d_araw, ds->h_araw))) return rc;
+    const BlReModel &m = ds->re;
+    const BlCombModel &cm = ds->comb;
+    p.rows = m.rows; p.ns = m.n_stride; p.N = m.n_sites; p.T = m.T; p.Ks = m.Ks; p.D = ds->D;
+    p.pc = BlCombPredBlock{cm.Jpc, cm.Kpc, m.Ks + 1, ds->d_wraw};
+    p.aru = BlCombPredBlock{cm.Jaru, cm.Karu, m.Ks + cm.Kpc + 2, ds->d_araw};
+    p.Js = cm.Jsc; p.o_x = m.G0;
+    return BL_OK;
+}
+
+extern "C" int bl_predict_comb(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, uint8_t *z, uint8_t *y_pc, uint8_t *y_aru,
+                               float *scores)
+{
+    int rc = per_draw_front("bl_predict_comb", ds, n_draws, draws, z || y_pc || y_aru || scores, serves_comb,
+                            "occu_comb only; the other models use bl_predict / bl_predict_counts / bl_predict_scores");
+    BlCombPredParams p{};
+    if (rc || (rc = comb_predict_params(ds, p))) return rc;
+    p.seed = (unsigned long long)seed;
+    const size_t cells = (size_t)p.T * p.N; // per draw
+    const DrawOut outs[] = {{z, cells, (void **)&p.z, false},
+                            {y_pc, cells * p.pc.J, (void **)&p.y_pc, false},   // (an empty block: skipped)
+                            {y_aru, cells * p.aru.J, (void **)&p.y_aru, false},
+                            {scores, cells * p.Js * 4, (void **)&p.scores, false}};
+    size_t largest = cells;
+    for (const DrawOut &o : outs) if (o.host) largest = std::max(largest, o.bytes);
+    return run_over_draws(ds, n_draws, draws, largest, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
+        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
+        return (hipError_t)bl_launch_comb_predict(&p, grid_y, nullptr);
+    });
+}
+
+extern "C" int bl_deterministic_comb(bl_dataset *ds, int n_draws, const float *draws, float *psi, float *pc_prob, float *aru_prob)
+{
+    int rc = per_draw_front("bl_deterministic_comb", ds, n_draws, draws, psi || pc_prob || aru_prob, serves_comb,
+                            "occu_comb only; the other models use bl_deterministic");
+    BlCombPredParams p{};
+    if (rc || (rc = comb_predict_params(ds, p))) return rc;
+    const size_t cells = (size_t)p.T * p.N; // per draw
+    const DrawOut outs[] = {{psi, cells * 4, (void **)&p.psi, false},
+                            {pc_prob, cells * p.pc.J * 4, (void **)&p.pc_prob, false},
+                            {aru_prob, cells * p.aru.J * 4, (void **)&p.aru_prob, false}};
+    size_t largest = cells * 4;
+    for (const DrawOut &o : outs) if (o.host) largest = std::max(largest, o.bytes);
+    return run_over_draws(ds, n_draws, draws, largest, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
+        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
+        return (hipError_t)bl_launch_comb_deterministic(&p, grid_y, nullptr);
     });
 }
 
@@ -1127,6 +1190,7 @@ extern "C" int bl_dataset_destroy(bl_dataset *ds)
     if (ds->in_flight) { *ds->h_abort = 1; hipStreamSynchronize(ds->stream); }
     if (ds->d_rows) hipFree(ds->d_rows);
     if (ds->d_wraw) hipFree(ds->d_wraw);
+    if (ds->d_araw) hipFree(ds->d_araw);
     if (ds->d_tab) hipFree(ds->d_tab);
     if (ds->d_dur) hipFree(ds->d_dur);
     if (ds->d_ccell) hipFree(ds->d_ccell);
@@ -1712,6 +1776,15 @@ extern "C" int bl_dataset_create_comb(const bl_comb_dims *cd, const float *site_
     const int ns = ds->n_stride, vp = Kp + 1, va = Ka + 1, KSc = Ks + 1;
     const int r_pc = KSc, r_ar = r_pc + T * Jp * vp, r_per = r_ar + T * Ja * va, n_rows = r_per + 6 * T;
     std::vector<float> rows((size_t)n_rows * ns, 0.0f);
+    // the ARU block's raw covariates, NaN -> 0, as dataset_create_impl keeps the point counts' (h_wraw): the rows below are folded by the
+    // observation, so bl_predict_comb / bl_deterministic_comb, which withhold it, read these
+    ds->h_araw.assign((size_t)std::max(T * Ja * Ka, 1) * ns, 0.0f);
+    for (int i = 0; i < N; i++)
+        for (int v = 0; v < T * Ja; v++)
+            for (int k = 0; k < Ka; k++) {
+                const float x = aru_covs[((size_t)i * T * Ja + v) * Ka + k];
+                ds->h_araw[((size_t)v * Ka + k) * ns + i] = std::isnan(x) ? 0.0f : x;
+            }
     const double LOG_TINY = -87.33654475055310898657;
     for (int i = 0; i < N; i++) {
         bool site_nan = false;

@@ -548,6 +548,25 @@ class OccuDataset:
                               [(True, cell, np.float32), (True, cell, np.float32), (True, cell, np.uint8),
                                (visits, visit, np.float32), (visits, visit, np.int32)])
 
+    def predictive_comb(self, draws, seed: int = 0, z: bool = True, y_pc: bool = True, y_aru: bool = True, scores: bool = True):
+        """Posterior predictive of an occu_comb handle for draws (n, D), all three observed sites withheld: ``z`` (n, T, N) uint8 ~
+        Bernoulli(psi); ``y_pc`` (n, Jpc, T, N) and ``y_aru`` (n, Jaru, T, N) uint8; ``scores`` (n, Js, T, N) float32.  Every output is
+        a function of (seed, draw, period, site) only and does not depend on which others are asked for (``None`` where not wanted)
+        (include/biolith_hip.h: bl_predict_comb); builder-defined: the reference's predict cannot withhold the scores."""
+        cell = (self.T, self.N)
+        return self._per_draw(self._lib.bl_predict_comb, draws, seed,
+                              [(z, cell, np.uint8), (y_pc, (self.J,) + cell, np.uint8), (y_aru, (getattr(self, "Ja", 0),) + cell, np.uint8),
+                               (scores, (getattr(self, "Js", 0),) + cell, np.float32)])   # (another model's handle: the entry refuses it)
+
+    def deterministic_comb(self, draws, psi: bool = True, pc_prob: bool = True, aru_prob: bool = True):
+        """occu_comb's deterministic sites for draws (n, D): ``psi`` (n, T, N), ``PC_prob_detection`` (n, Jpc, T, N) and
+        ``ARU_prob_detection`` (n, Jaru, T, N), float32, ``None`` where not wanted (include/biolith_hip.h: bl_deterministic_comb;
+        occu_comb.py:224-331)."""
+        cell = (self.T, self.N)
+        fn = lambda h, n, d, seed, *outs: self._lib.bl_deterministic_comb(h, n, d, *outs)   # (the entry takes no seed)
+        return self._per_draw(fn, draws, 0, [(psi, cell, np.float32), (pc_prob, (self.J,) + cell, np.float32),
+                                             (aru_prob, (getattr(self, "Ja", 0),) + cell, np.float32)])
+
 
 def _predictive_scores(self, draws, seed: int = 0):
     """occu_cs: posterior predictive ``z`` (n, T, N), ``f`` (n, J, T, N) as uint8 and the scores ``s`` (n, J, T, N) float32

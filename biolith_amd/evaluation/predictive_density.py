@@ -60,7 +60,8 @@ def log_likelihood(model_fn: Callable, posterior_samples: Dict[str, np.ndarray],
     >>> log_likelihood(occu, preds, **data)
     """
     if getattr(model_fn, "__biolith_amd_model__", None) == "occu_comb":
-        raise NotImplementedError("log_likelihood / lppd / waic: not built for occu_comb (its three observed sites are a later addition)")
+        raise NotImplementedError("log_likelihood / lppd / waic: not built for occu_comb (one observed site per call; its three are served by "
+                                  "log_likelihood_comb / waic_comb on predict_comb's output)")
     ps = {k: v for k, v in posterior_samples.items() if k not in observation_keys}
     obs = np.asarray(kwargs["obs"], dtype=np.float32)
     valid = _valid_obs(kwargs["site_covs"], kwargs["obs_covs"], obs).transpose((3, 2, 1, 0))  # (J, T, N, S)
@@ -171,4 +172,66 @@ def waic(model_fn: Callable, posterior_samples: Dict[str, np.ndarray], **kwargs)
 def waic_manual(posterior_samples: Dict[str, np.ndarray], data: Dict[str, np.ndarray]) -> Dict[str, float]:
     """WAIC from the marginal ``psi * p`` likelihood (waic.py:85-124)."""
     l, p = _pointwise(_manual_ll(posterior_samples, data))
+    return {"waic": -2 * (l - p), "p_waic": p, "lppd": l}
+
+
+# ---- occu_comb: three observed sites (y_pc, y_aru, scores) behind one z -- BUILDER-DEFINED, the consumers of ``predict_comb()`` ----
+def _comb_valid(data):
+    """{block: (S, N, T, J) mask of the entries that enter occu_comb's likelihood}: a visit is masked by its y, its block's covariates
+    and the site covariates; a score by itself and the site covariates only (occu_comb.py:161-186)."""
+    site = np.isfinite(np.asarray(data["site_covs"], dtype=np.float64)).all(axis=-1)[None, :, None, None]
+    out = {}
+    for key, obs, covs in (("y_pc", "PC_obs", "PC_obs_covs"), ("y_aru", "ARU_obs", "ARU_obs_covs")):
+        out[key] = (np.isfinite(np.asarray(data[obs], dtype=np.float64)) & site
+                    & np.isfinite(np.asarray(data[covs], dtype=np.float64)).all(axis=-1)[None])
+    out["scores"] = np.isfinite(np.asarray(data["scores_obs"], dtype=np.float64)) & site
+    return out
+
+
+def log_likelihood_comb(posterior_samples: Dict[str, np.ndarray], **data) -> Dict[str, np.ndarray]:
+    """Log-likelihood of every observation of ``occu_comb``'s three observed sites under every predictive draw:
+    ``{"y_pc": (n, Jpc, T, N, S), "y_aru": (n, Jaru, T, N, S), "scores": (n, Js, T, N, S)}``, float32.
+
+    ``posterior_samples`` is what :func:`biolith_amd.utils.predict_comb` returned (the sites ``z``, ``PC_prob_detection``,
+    ``ARU_prob_detection`` and the posterior's ``ARU_prob_fp_constant``, ``ARU_fp_unoccupied``, ``mu0``, ``mu1``, ``sigma0``, ``sigma1``);
+    ``data`` carry ``site_covs``, ``PC_obs_covs``, ``ARU_obs_covs``, ``PC_obs``, ``ARU_obs`` and ``scores_obs`` (anything else, e.g.
+    ``coords`` / ``ell``, is ignored).  Per draw, at its sampled z (occu_comb.py:300-349):
+    ``y_pc ~ Bernoulli(z p_pc)``, ``y_aru ~ Bernoulli(1 - (1 - z p_aru)(1 - fc)(1 - (1 - z) fu))``, both probabilities clamped to
+    float32's ``[tiny, 1 - eps]`` as NumPyro clamps them (a point-count detection at z = 0 costs ``log tiny``), and
+    ``scores ~ Normal(z ? mu1 : mu0, z ? sigma1 : sigma0)`` as the ``occu_cs`` branch of :func:`log_likelihood` states it.  Masked
+    entries are 0.  The terms are evaluated in float64 from the float32 sites.
+
+    Examples
+    --------
+    >>> preds = predict_comb(occu_comb, results.mcmc, **data)
+    >>> ll = log_likelihood_comb(preds, **data)
+    """
+    ps = posterior_samples
+    valid = {k: v.transpose((3, 2, 1, 0)) for k, v in _comb_valid(data).items()}            # (J, T, N, S)
+    z = np.asarray(ps["z"], dtype=np.float64)[:, None]                                      # (n, 1, T, N, S)
+    plate = lambda k: np.asarray(ps[k], dtype=np.float64).reshape((z.shape[0],) + (1,) * 3 + (-1,))
+    fc, fu = plate("ARU_prob_fp_constant"), plate("ARU_fp_unoccupied")
+
+    def bernoulli(key, obs, prob):
+        y = np.where(valid[key], np.asarray(data[obs], dtype=np.float64).transpose((3, 2, 1, 0)), 0.0)[None]
+        prob = np.clip(prob, float(_TINY), float(_ONE_MINUS_EPS))
+        return np.where(valid[key][None], np.where(y > 0, np.log(prob), np.log1p(-prob)), 0.0).astype(np.float32)
+
+    out = {"y_pc": bernoulli("y_pc", "PC_obs", z * np.asarray(ps["PC_prob_detection"], dtype=np.float64))}
+    p_aru = np.asarray(ps["ARU_prob_detection"], dtype=np.float64)
+    out["y_aru"] = bernoulli("y_aru", "ARU_obs", 1.0 - (1.0 - z * p_aru) * (1.0 - fc) * (1.0 - (1.0 - z) * fu))
+    mu, sg = np.where(z > 0, plate("mu1"), plate("mu0")), np.where(z > 0, plate("sigma1"), plate("sigma0"))
+    sc = np.where(valid["scores"], np.asarray(data["scores_obs"], dtype=np.float64).transpose((3, 2, 1, 0)), 0.0)[None]
+    ll = -0.5 * ((sc - mu) / sg) ** 2 - np.log(sg) - 0.5 * np.log(2 * np.pi)
+    out["scores"] = np.where(valid["scores"][None], ll, 0.0).astype(np.float32)
+    return out
+
+
+def waic_comb(posterior_samples: Dict[str, np.ndarray], **data) -> Dict[str, float]:
+    """``{"waic": -2 (lppd - p_waic), "p_waic", "lppd"}`` of ``occu_comb`` over the valid entries of its three observed sites together
+    (every point-count visit, ARU visit and score is one point), from :func:`log_likelihood_comb`."""
+    ll = log_likelihood_comb(posterior_samples, **data)
+    valid = _comb_valid(data)
+    points = np.concatenate([ll[k].transpose((0, 4, 3, 2, 1))[:, valid[k]].astype(np.float64) for k in ("y_pc", "y_aru", "scores")], axis=1)
+    l, p = _pointwise(points)
     return {"waic": -2 * (l - p), "p_waic": p, "lppd": l}

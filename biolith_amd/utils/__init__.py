@@ -5,8 +5,9 @@ from .grid_search import GridSearchResult, grid_search_priors
 from .init import init_to_feasible, init_to_mean, init_to_median, init_to_sample, init_to_uniform, init_to_value
 from .latent import conditional_occupancy
 from .predict import predict
+from .predict_comb import predict_comb
 from .scores import conditional_scores
 from .counts import conditional_counts
 
-__all__ = ["fit", "FitResult", "predict", "conditional_occupancy", "conditional_abundance", "conditional_dynamics", "conditional_scores", "conditional_counts", "grid_search_priors", "GridSearchResult", "init_to_uniform", "init_to_feasible", "init_to_value",
+__all__ = ["fit", "FitResult", "predict", "predict_comb", "conditional_occupancy", "conditional_abundance", "conditional_dynamics", "conditional_scores", "conditional_counts", "grid_search_priors", "GridSearchResult", "init_to_uniform", "init_to_feasible", "init_to_value",
            "init_to_mean", "init_to_median", "init_to_sample"]

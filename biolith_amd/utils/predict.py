@@ -68,7 +68,7 @@ def predict(
     if not callable(model_fn) or getattr(model_fn, "__biolith_amd_model__", None) is None:
         raise TypeError("predict(): model_fn must be a biolith_amd model (biolith_amd.models.occu / occu_rn)")
     if getattr(model_fn, "__biolith_amd_model__", None) == "occu_comb":
-        raise NotImplementedError("predict(): not built for occu_comb (its posterior predictive is a later addition)")
+        raise NotImplementedError("predict(): not built for occu_comb (the reference's predict cannot withhold its scores); use predict_comb")
     infer_discrete = bool(infer_discrete)   # (same sites, same distribution: see the docstring)
     # (no warning: the reference hands the flag to Predictive silently, predict.py:67-72, and pipelines that run with warnings as
     # errors must not break on a design caveat -- the caveat is the docstring's and DESIGN.md section 3's)

@@ -217,7 +217,8 @@ int bl_dataset_create_cs(const bl_dims *dims, const float *site_covs, const floa
  * with fc ~ Beta(prior_fc), fu ~ Beta(prior_fu), mu0 ~ Normal(prior_mu[0..1]), mu1 ~ Normal(prior_mu[2..3]) truncated below at mu0,
  * sigma_f ~ Gamma(prior_sigma[2f], prior_sigma[2f+1]); beta ~ prior_beta, both alphas ~ prior_alpha (bl_dataset_set_prior_family
  * applies).  At most 16 covariates per block.  bl_logp_grad and bl_nuts_* serve the handle (the random-effects kernels' framework);
- * bl_deterministic / bl_predict* do not: psi and the detection probabilities are formed by the caller from the draws.
+ * bl_deterministic / bl_predict* do not (the fit's sites are formed by the caller from the draws); the model's own entries are
+ * bl_deterministic_comb and bl_predict_comb.
  */
 typedef struct bl_comb_dims {
     int32_t n_sites, n_periods;           /* N, T                                          */
@@ -364,6 +365,28 @@ int bl_predict_counts(bl_dataset *ds, int n_draws, const float *draws, uint64_t 
 /* Same for occu_cs (occu_cs.py:196-232 with obs withheld): z[n][T][N], f[n][J][T][N] (which score distribution a replicate
  * drew from) as bytes, s[n][J][T][N] the scores; any of the three may be NULL. */
 int bl_predict_scores(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, uint8_t *latent, uint8_t *f, float *s);
+
+/*
+ * Posterior predictive of occu_comb -- BUILDER-DEFINED: the reference's predict cannot withhold scores_obs from this model (a required
+ * positional argument, models/occu_comb.py:19-24, 340-349), so under its Predictive the scores stay pinned to the data while y_pc / y_aru
+ * are drawn.  Here all three observed sites are drawn, one replicate data set per posterior draw
+ * [beta | alpha_PC | alpha_ARU | logit fc | logit fu | mu0 | log(mu1 - mu0) | log sigma0 | log sigma1]:
+ *   z      [n_draws][T][N]       ~ Bernoulli(psi)
+ *   y_pc   [n_draws][Jpc][T][N]  ~ Bernoulli(z p_pc)
+ *   y_aru  [n_draws][Jaru][T][N] ~ Bernoulli(1 - (1 - z p_aru)(1 - fc)(1 - (1 - z) fu))
+ *   scores [n_draws][Js][T][N]   ~ Normal(z ? mu1 : mu0, z ? sigma1 : sigma0)
+ * bytes / float32 on the host, NULL = skip (all four NULL: BL_ERR_INVALID); a block without replicates is empty.  Covariates that are
+ * NaN read as 0 and nothing is masked, as with the observations withheld.  The cell's generator is bl_predict's; it is consumed in one
+ * fixed order (z, the point counts, the ARU visits, two uniforms per score), so the sample is a function of (seed, draw, period, site)
+ * only and no output depends on which others are asked for.  Serves handles of bl_dataset_create_comb; every other handle:
+ * BL_ERR_UNSUPPORTED, the message names the model.  BL_ERR_BUSY while a NUTS launch is in flight on the handle.
+ */
+int bl_predict_comb(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, uint8_t *z, uint8_t *y_pc, uint8_t *y_aru,
+                    float *scores);
+/* occu_comb's deterministic sites (occu_comb.py:224-331), as bl_deterministic forms the other models': psi [n_draws][T][N] (constant over
+ * T), pc_prob [n_draws][Jpc][T][N] = sigmoid(alpha_PC . (1, w_pc)), aru_prob [n_draws][Jaru][T][N] = sigmoid(alpha_ARU . (1, w_aru));
+ * host float32, NULL = skip.  Serves handles of bl_dataset_create_comb only (BL_ERR_UNSUPPORTED otherwise, the message names the model). */
+int bl_deterministic_comb(bl_dataset *ds, int n_draws, const float *draws, float *psi, float *pc_prob, float *aru_prob);
 
 /*
  * Conditional occupancy -- BUILDER-DEFINED, NO REFERENCE COUNTERPART (biolith/utils/predict.py withholds the observations, so its z
