@@ -26,6 +26,7 @@
 #include "score_posterior.hpp"
 #include "count_posterior.hpp"
 #include "comb_predict.hpp"
+#include "predictive_check.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -310,7 +311,7 @@ extern "C" int bl_device_count(int *count)
 }
 
 // ------------------------------------------------------------------ the per-draw entries ----
-// bl_predict, bl_predict_scores, bl_predict_counts, bl_predict_comb, bl_deterministic_comb, bl_site_posterior, bl_abundance_posterior, bl_path_posterior, bl_score_posterior and
+// bl_predict, bl_predict_scores, bl_predict_counts, bl_predict_comb, bl_deterministic_comb, bl_predictive_check, bl_site_posterior, bl_abundance_posterior, bl_path_posterior, bl_score_posterior and
 // bl_count_posterior run one kernel over (site, posterior draw).  What they share is stated once: the name of a handle's model, the checks in front, the rows that go up on
 // first use, and the driver that takes the draws through the kernel in chunks.
 
@@ -759,6 +760,63 @@ extern "C" int bl_deterministic_comb(bl_dataset *ds, int n_draws, const float *d
         p.draws = d_draws; p.n0 = n0; p.n1 = n1;
         return (hipError_t)bl_launch_comb_deterministic(&p, grid_y, nullptr);
     });
+}
+
+// ---- the posterior predictive check, fused: two discrepancies of the observed and of the replicate data per posterior draw ----
+// (biolith/evaluation/posterior_predictive_check.py:17-160 on predict()'s y and psi * prob_detection.)  Kernels: predictive_check.hip.
+// They regenerate bl_predict's replicate and bl_deterministic's psi and p, so they read what those read: the head of the handle's rows and
+// the raw observation covariates.  The observations come from the caller (the handle's rows fold the covariate masks into theirs; the
+// check masks by the observation alone); their count per revisit does not depend on the draw and is formed here.  The blocks' partials are
+// workspace of the draws' chunk; the results are 32 bytes a draw.
+extern "C" int bl_predictive_check(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, const uint8_t *obs, double *by_site,
+                                   double *by_revisit)
+{
+    int rc = per_draw_front("bl_predictive_check", ds, n_draws, draws, obs && (by_site || by_revisit),
+                            [](const bl_dataset *d) { return d->nsp == 1 && (d->model == 0 || d->model == 2 || re_kind_in(d, {0, 2})); },
+                            "occu, with or without false positives / random effects: the handles of bl_predict without occu_rn");
+    if (rc || (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
+    const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates, TJ = T * J;
+    std::vector<int> obs_visit((size_t)TJ, 0);
+    for (int j = 0; j < J; j++)
+        for (int t = 0; t < T; t++) {
+            const uint8_t *row = obs + ((size_t)j * T + t) * N;
+            int c = 0;
+            for (int i = 0; i < N; i++) {
+                if (row[i] > 1 && row[i] != 255) return bl_fail(BL_ERR_INVALID, "bl_predictive_check: obs holds %d (0, 1, or 255 = not observed)", (int)row[i]);
+                c += row[i] == 1;
+            }
+            obs_visit[(size_t)t * J + j] = c;
+        }
+    BlPredCheckParams p{};
+    p.rows = ds->d_rows; p.wraw = ds->d_wraw; p.ns = ds->n_stride; p.N = N; p.T = T; p.J = J; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = ds->D;
+    p.seed = (unsigned long long)seed;
+    p.o_u = p.o_v = p.o_e = p.o_fp = -1;
+    if (ds->model == 2) { p.fp_mode = ds->fp_mode; p.o_fp = ds->D - 1; }
+    if (ds->model == 6) {
+        const BlReModel &m = ds->re;
+        if (m.kind == 2) { p.fp_mode = m.fp_mode; p.o_fp = m.o_fp; }
+        p.o_u = m.o_u; p.o_v = m.o_v; p.o_e = m.o_e;
+    }
+    p.n_blocks = (N + BL_PC_THREADS - 1) / BL_PC_THREADS;
+    DevScratch scratch;
+    unsigned char *d_obs = nullptr;
+    int *d_obs_visit = nullptr;
+    BL_HIP(scratch.alloc((void **)&d_obs, (size_t)TJ * N));
+    BL_HIP(hipMemcpy(d_obs, obs, (size_t)TJ * N, hipMemcpyHostToDevice));
+    BL_HIP(scratch.alloc((void **)&d_obs_visit, (size_t)TJ * 4));
+    BL_HIP(hipMemcpy(d_obs_visit, obs_visit.data(), (size_t)TJ * 4, hipMemcpyHostToDevice));
+    p.obs = d_obs; p.obs_visit = d_obs_visit;
+    const size_t nb = (size_t)p.n_blocks;
+    const DrawOut outs[] = {{by_site, 32, (void **)&p.by_site, false},
+                            {by_revisit, 32, (void **)&p.by_revisit, false},
+                            {nullptr, by_site ? nb * 32 : 0, (void **)&p.site_part, true},
+                            {nullptr, by_revisit ? nb * TJ * 8 : 0, (void **)&p.visit_exp, true},
+                            {nullptr, by_revisit ? nb * TJ * 4 : 0, (void **)&p.visit_rep, true}};
+    return run_over_draws(ds, n_draws, draws, std::max<size_t>(32, nb * std::max(32, TJ * 8)), outs,
+                          [&](const float *d_draws, int n0, int n1, int grid_y) {
+                              p.draws = d_draws; p.n0 = n0; p.n1 = n1;
+                              return (hipError_t)bl_launch_predictive_check(&p, grid_y, nullptr);
+                          });
 }
 
 // ---- predictive counts of the count models (occu_cop, nmixture) ----

@@ -83,7 +83,7 @@ class _PinnedPool:
 
 
 _PINNED = _PinnedPool()
-_CTYPE = {np.float32: C.c_float, np.uint8: C.c_uint8, np.int32: C.c_int32}   # the per-draw entries' output types
+_CTYPE = {np.float32: C.c_float, np.uint8: C.c_uint8, np.int32: C.c_int32, np.float64: C.c_double}   # the per-draw entries' output types
 
 
 @dataclass
@@ -491,6 +491,22 @@ class OccuDataset:
         dt = np.int32 if counts else np.uint8
         return self._per_draw(self._lib.bl_predict_counts if counts else self._lib.bl_predict, draws, seed,
                               [(latent, (self.T, self.N), dt), (y, (self.J, self.T, self.N), dt)], pinned=False)
+
+    def predictive_check(self, draws, obs, seed: int = 0, by_site: bool = True, by_revisit: bool = True):
+        """The posterior predictive check's discrepancies for draws (n, D), fused on the device: ``by_site`` and ``by_revisit``, each
+        (n, 4) float64 = ``ft_obs, ft_rep, chi_obs, chi_rep`` (Freeman-Tukey and chi-squared, of the observed and of the replicate data)
+        or ``None``.  ``obs`` is (N, T, J), NaN = not observed, else 0 / 1; the replicate is ``predictive(draws, seed)``'s ``y`` and the
+        expectation ``deterministic``'s ``psi * prob_detection``, neither of which is materialised.  occu handles with or without false
+        positives / random effects (include/biolith_hip.h: bl_predictive_check; posterior_predictive_check.py:17-160)."""
+        o = np.asarray(obs, dtype=np.float32)
+        if o.shape != (self.N, self.T, self.J):
+            raise ValueError(f"obs must have shape (n_sites, n_periods, n_replicates) = {(self.N, self.T, self.J)}, got {o.shape}")
+        seen = np.isfinite(o)
+        if not np.isin(o[seen], (0.0, 1.0)).all():
+            raise ValueError("obs must hold 0, 1 or NaN")
+        o8 = np.ascontiguousarray(np.where(seen, o, 255.0).astype(np.uint8).transpose(2, 1, 0))   # (J, T, N)
+        fn = lambda h, n, d, s, *outs: self._lib.bl_predictive_check(h, n, d, s, o8.ctypes.data_as(C.POINTER(C.c_uint8)), *outs)
+        return self._per_draw(fn, draws, seed, [(by_site, (4,), np.float64), (by_revisit, (4,), np.float64)], pinned=False)
 
     def site_posterior(self, draws, seed: int = 0, log_lik: bool = True, z_prob: bool = True, z: bool = True):
         """Conditional occupancy for draws (n, D), each output (n, T, N): ``log_lik`` float32, the z-marginalised log-likelihood of a

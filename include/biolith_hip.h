@@ -389,6 +389,25 @@ int bl_predict_comb(bl_dataset *ds, int n_draws, const float *draws, uint64_t se
 int bl_deterministic_comb(bl_dataset *ds, int n_draws, const float *draws, float *psi, float *pc_prob, float *aru_prob);
 
 /*
+ * The posterior predictive check (biolith/evaluation/posterior_predictive_check.py:17-160), fused: per posterior draw the discrepancy of
+ * the observed and of a replicate data set against E = psi * prob_detection, without the replicate-level arrays y and prob_detection
+ * [n_draws][J][T][N] that the host check reduces.  The replicate is bl_predict's y for the same seed, bit for bit (the cell's generator,
+ * consumed in its order, the same arithmetic); E is the float64 product of bl_deterministic's float32 psi and prob_detection, which is
+ * exact; a visit counts where obs != 255 and by nothing else.  Float64 throughout:
+ *   ft(o, e) = (sqrt o - sqrt e)^2,   chi(o, e) = (o - e)^2 / (e + 1e-10)
+ *   by_site:    o, y and E summed over the site's seen visits (t, j), the statistic, summed over sites
+ *   by_revisit: o, y and E of revisit (t, j) summed over its seen sites, the statistic, summed over (t, j)
+ * obs is [J][T][N] bytes on the host: 0, 1, or 255 = not observed (anything else: BL_ERR_INVALID).  It is passed and not taken from the
+ * handle, whose rows also fold in the covariate masks.  by_site / by_revisit are [n_draws][4] float64 on the host, a draw's four being
+ * ft_obs, ft_rep, chi_obs, chi_rep; NULL = skip, and a skipped output never changes the other (both NULL: BL_ERR_INVALID).  Sums run in a
+ * fixed order (registers, LDS, one partial per site block, the blocks in order; no floating-point atomics): two calls return the same
+ * bits.  Serves the occupancy handles of bl_predict, one species each: bl_dataset_create, _fp, _re, _re_fp; every other handle:
+ * BL_ERR_UNSUPPORTED, the message names the model.  BL_ERR_BUSY while a NUTS launch is in flight on the handle.
+ */
+int bl_predictive_check(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, const uint8_t *obs, double *by_site,
+                        double *by_revisit);
+
+/*
  * Conditional occupancy -- BUILDER-DEFINED, NO REFERENCE COUNTERPART (biolith/utils/predict.py withholds the observations, so its z
  * is drawn from the prior).  Per posterior draw and (period, site), with the site-period's unmasked observations `obs`:
  *   A = log psi + log p(obs | z = 1),   B = log(1 - psi) + log p(obs | z = 0)         (the terms, clamps and masks of bl_logp_grad)
