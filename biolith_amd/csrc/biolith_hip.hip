@@ -27,6 +27,7 @@
 #include "count_posterior.hpp"
 #include "comb_predict.hpp"
 #include "predictive_check.hpp"
+#include "predictive_density.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -768,12 +769,13 @@ extern "C" int bl_deterministic_comb(bl_dataset *ds, int n_draws, const float *d
 // the raw observation covariates.  The observations come from the caller (the handle's rows fold the covariate masks into theirs; the
 // check masks by the observation alone); their count per revisit does not depend on the draw and is formed here.  The blocks' partials are
 // workspace of the draws' chunk; the results are 32 bytes a draw.
+// what bl_predictive_check and bl_predictive_density serve
+static bool serves_occu(const bl_dataset *d) { return d->nsp == 1 && (d->model == 0 || d->model == 2 || re_kind_in(d, {0, 2})); }
+static const char *const SERVES_OCCU = "occu, with or without false positives / random effects: the handles of bl_predict without occu_rn";
 extern "C" int bl_predictive_check(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, const uint8_t *obs, double *by_site,
                                    double *by_revisit)
 {
-    int rc = per_draw_front("bl_predictive_check", ds, n_draws, draws, obs && (by_site || by_revisit),
-                            [](const bl_dataset *d) { return d->nsp == 1 && (d->model == 0 || d->model == 2 || re_kind_in(d, {0, 2})); },
-                            "occu, with or without false positives / random effects: the handles of bl_predict without occu_rn");
+    int rc = per_draw_front("bl_predictive_check", ds, n_draws, draws, obs && (by_site || by_revisit), serves_occu, SERVES_OCCU);
     if (rc || (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
     const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates, TJ = T * J;
     std::vector<int> obs_visit((size_t)TJ, 0);
@@ -817,6 +819,67 @@ extern "C" int bl_predictive_check(bl_dataset *ds, int n_draws, const float *dra
                               p.draws = d_draws; p.n0 = n0; p.n1 = n1;
                               return (hipError_t)bl_launch_predictive_check(&p, grid_y, nullptr);
                           });
+}
+
+// ---- the information criteria's two reductions of the pointwise log-likelihood, fused ----
+// (biolith/evaluation/log_likelihood.py:10-96 under lppd.py, waic.py and deviance.py.)  Kernels: predictive_density.hip.  They read what
+// bl_predictive_check reads and the caller's observation bytes, in which 255 now carries every mask.  The per-draw sums go through the
+// draws in chunks whose block partials stay within 256 MB; the per-point statistics are one launch over all the draws (its strip
+// partials do not grow with them), so no chunking can split them.
+extern "C" int bl_predictive_density(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, const uint8_t *obs, int marginal,
+                                     double *per_draw, double *point_lse, double *point_var)
+{
+    int rc = per_draw_front("bl_predictive_density", ds, n_draws, draws, obs && (per_draw || point_lse || point_var), serves_occu,
+                            SERVES_OCCU);
+    if (rc || (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
+    const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates;
+    const size_t cells = (size_t)T * J * N;
+    for (size_t c = 0; c < cells; c++)
+        if (obs[c] > 1 && obs[c] != 255)
+            return bl_fail(BL_ERR_INVALID, "bl_predictive_density: obs holds %d (0, 1, or 255 = not a point)", (int)obs[c]);
+    BlPredDensityParams p{};
+    p.rows = ds->d_rows; p.wraw = ds->d_wraw; p.ns = ds->n_stride; p.N = N; p.T = T; p.J = J; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = ds->D;
+    p.seed = (unsigned long long)seed;
+    p.marginal = marginal ? 1 : 0;
+    p.n_draws = n_draws;
+    p.o_u = p.o_v = p.o_e = p.o_fp = -1;
+    if (ds->model == 2) { p.fp_mode = ds->fp_mode; p.o_fp = ds->D - 1; }
+    if (ds->model == 6) {
+        const BlReModel &m = ds->re;
+        if (m.kind == 2) { p.fp_mode = m.fp_mode; p.o_fp = m.o_fp; }
+        p.o_u = m.o_u; p.o_v = m.o_v; p.o_e = m.o_e;
+    }
+    DevScratch scratch;
+    float *d_draws = nullptr;
+    unsigned char *d_obs = nullptr;
+    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * ds->D * 4));
+    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * ds->D * 4, hipMemcpyHostToDevice));
+    BL_HIP(scratch.alloc((void **)&d_obs, cells));
+    BL_HIP(hipMemcpy(d_obs, obs, cells, hipMemcpyHostToDevice));
+    p.draws = d_draws; p.obs = d_obs;
+    if (per_draw) {
+        p.n_blocks = (N + BL_PD_THREADS - 1) / BL_PD_THREADS;
+        const size_t fit = ((size_t)256 << 20) / ((size_t)p.n_blocks * 8); // draws whose block partials fill 256 MB
+        const int chunk = (int)std::min<size_t>((size_t)n_draws, std::max<size_t>(1, fit));
+        BL_HIP(scratch.alloc((void **)&p.draw_part, (size_t)chunk * p.n_blocks * 8));
+        BL_HIP(scratch.alloc((void **)&p.per_draw, (size_t)n_draws * 8));
+        for (int n0 = 0; n0 < n_draws; n0 += chunk) {
+            p.n0 = n0; p.n1 = std::min(n0 + chunk, n_draws);
+            BL_HIP((hipError_t)bl_launch_predictive_density_draws(&p, std::min(p.n1 - p.n0, 1024), nullptr));
+        }
+        BL_HIP(hipMemcpy(per_draw, p.per_draw, (size_t)n_draws * 8, hipMemcpyDeviceToHost));
+    }
+    if (point_lse || point_var) {
+        // strips of draws on grid.y: as many as let cells * strips fill the device, whatever the draw count
+        p.strips = (int)std::min<size_t>(BL_PD_MAX_STRIPS, std::max<size_t>(1, (BL_PD_FILL + cells - 1) / cells));
+        BL_HIP(scratch.alloc((void **)&p.strip_part, (size_t)p.strips * 4 * cells * 8));
+        if (point_lse) BL_HIP(scratch.alloc((void **)&p.point_lse, cells * 8));
+        if (point_var) BL_HIP(scratch.alloc((void **)&p.point_var, cells * 8));
+        BL_HIP((hipError_t)bl_launch_predictive_density_points(&p, nullptr));
+        if (point_lse) BL_HIP(hipMemcpy(point_lse, p.point_lse, cells * 8, hipMemcpyDeviceToHost));
+        if (point_var) BL_HIP(hipMemcpy(point_var, p.point_var, cells * 8, hipMemcpyDeviceToHost));
+    }
+    return BL_OK;
 }
 
 // ---- predictive counts of the count models (occu_cop, nmixture) ----

@@ -508,6 +508,32 @@ class OccuDataset:
         fn = lambda h, n, d, s, *outs: self._lib.bl_predictive_check(h, n, d, s, o8.ctypes.data_as(C.POINTER(C.c_uint8)), *outs)
         return self._per_draw(fn, draws, seed, [(by_site, (4,), np.float64), (by_revisit, (4,), np.float64)], pinned=False)
 
+    def predictive_density(self, draws, obs, seed: int = 0, marginal: bool = False, per_draw: bool = True, point_lse: bool = True,
+                           point_var: bool = True):
+        """The pointwise log-likelihood of ``obs`` under draws (n, D), reduced on the device without being stored: ``per_draw`` (n,)
+        = its sum over the points per draw; ``point_lse`` (N, T, J) = ``log mean exp`` over the draws per point; ``point_var`` (N, T, J) =
+        its variance over the draws, ddof 1 (0 for one draw); float64, or ``None``.  ``obs`` is (N, T, J): 0 / 1, NaN = not a point (the
+        caller folds the covariate masks in), where both point outputs are 0.  ``marginal=False`` is the log-likelihood at
+        ``predictive(draws, seed)``'s ``z`` (evaluation.log_likelihood), ``True`` the marginal ``psi * p`` form
+        (log_likelihood_manual).  occu handles with or without false positives / random effects (include/biolith_hip.h:
+        bl_predictive_density)."""
+        o = np.asarray(obs, dtype=np.float32)
+        if o.shape != (self.N, self.T, self.J):
+            raise ValueError(f"obs must have shape (n_sites, n_periods, n_replicates) = {(self.N, self.T, self.J)}, got {o.shape}")
+        seen = np.isfinite(o)
+        if not np.isin(o[seen], (0.0, 1.0)).all():
+            raise ValueError("obs must hold 0, 1 or NaN")
+        o8 = np.ascontiguousarray(np.where(seen, o, 255.0).astype(np.uint8).transpose(2, 1, 0))   # (J, T, N)
+        d = self._draw_matrix(draws)
+        n = d.shape[0]
+        out_draw = np.zeros(n) if per_draw else None
+        out_lse, out_var = (np.zeros((self.J, self.T, self.N)) if want else None for want in (point_lse, point_var))
+        if n:
+            ptrs = [None if a is None else a.ctypes.data_as(C.POINTER(C.c_double)) for a in (out_draw, out_lse, out_var)]
+            _ffi.check(self._lib.bl_predictive_density(self._h, n, _fp(d), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                       o8.ctypes.data_as(C.POINTER(C.c_uint8)), int(bool(marginal)), *ptrs))
+        return (out_draw,) + tuple(None if a is None else a.transpose(2, 1, 0) for a in (out_lse, out_var))
+
     def site_posterior(self, draws, seed: int = 0, log_lik: bool = True, z_prob: bool = True, z: bool = True):
         """Conditional occupancy for draws (n, D), each output (n, T, N): ``log_lik`` float32, the z-marginalised log-likelihood of a
         (period, site)'s unmasked observations; ``z_prob`` float32 = P(z = 1 | those observations, theta); ``z`` uint8 ~

@@ -408,6 +408,31 @@ int bl_predictive_check(bl_dataset *ds, int n_draws, const float *draws, uint64_
                         double *by_revisit);
 
 /*
+ * The information criteria's reductions of the pointwise log-likelihood (biolith/evaluation/log_likelihood.py:10-96 under lppd.py,
+ * waic.py and deviance.py), fused: the log-likelihood ll of every observation under every posterior draw, [n_draws][J][T][N], is formed
+ * on the device in float64 and reduced there -- over the points per draw, and over the draws per point -- without being stored.
+ * With psi and r the float32 values of bl_deterministic and y the observation:
+ *   marginal == 0 (log_likelihood): z = bl_predict's latent draw for the same seed, bit for bit (the first uniform of the (draw, period,
+ *     site) generator); prob = z r, or with a false-positive rate f (f_c = f if BL_FP_CONSTANT, f_u = f if BL_FP_UNOCCUPIED)
+ *     prob = 1 - (1 - z r)(1 - f_c)(1 - (1 - z) f_u) in float64, f = (float)(1 / (1 + exp(-(double)phi))) the float32 site value of the
+ *     draw's coordinate phi; prob clamped to [FLT_MIN, 1 - FLT_EPSILON];  ll = y log(prob) + (1 - y) log1p(-prob)
+ *   marginal != 0 (log_likelihood_manual): q = (double)psi (double)r;  ll = y log(clip(q, 1e-10, 1 - 1e-10)) + (1 - y) log(clip(1 - q,
+ *     1e-10, 1 - 1e-10)); no generator, and a false-positive rate is ignored
+ * obs is [J][T][N] bytes on the host: 0, 1, or 255 = not a point (anything else: BL_ERR_INVALID); the caller folds every mask into it
+ * (the observation, the visit's and the site's covariates).  A cell that is no point contributes nothing and draws nothing.
+ *   per_draw  [n_draws]    sum of ll over the points
+ *   point_lse [J][T][N]    log mean_n exp(ll) over all n_draws draws; 0 where the cell is no point
+ *   point_var [J][T][N]    variance of ll over the draws, ddof 1 (0 for n_draws == 1); 0 where the cell is no point
+ * float64 on the host, NULL = skip, and a skipped output never changes another (all NULL: BL_ERR_INVALID).  Every sum, the streaming
+ * log-sum-exp and the Welford / Chan variance run in a fixed order (no floating-point atomics): two calls return the same bits.  Device
+ * workspace: at most 64 * 4 doubles per cell and one double per (draw, 256-site block); nothing grows with n_draws * J * T * N.
+ * Serves what bl_predictive_check serves; every other handle: BL_ERR_UNSUPPORTED, the message names the model.  BL_ERR_BUSY while a NUTS
+ * launch is in flight on the handle.
+ */
+int bl_predictive_density(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, const uint8_t *obs, int marginal,
+                          double *per_draw, double *point_lse, double *point_var);
+
+/*
  * Conditional occupancy -- BUILDER-DEFINED, NO REFERENCE COUNTERPART (biolith/utils/predict.py withholds the observations, so its z
  * is drawn from the prior).  Per posterior draw and (period, site), with the site-period's unmasked observations `obs`:
  *   A = log psi + log p(obs | z = 1),   B = log(1 - psi) + log p(obs | z = 0)         (the terms, clamps and masks of bl_logp_grad)
