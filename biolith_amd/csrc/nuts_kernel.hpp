@@ -211,6 +211,19 @@ struct BlSpinBound {
 #ifndef BL_POLL_NB
 #define BL_POLL_NB 2 // batches of 8 polls per lane in flight at once when a chain has more workgroups than one batch covers (A/B: 1 = one after the other)
 #endif
+#ifndef BL_RESIDENT_REC
+#define BL_RESIDENT_REC 1 // the lean plain-model kernels keep a lane's pair record in registers for the whole launch; 0: read from LDS every tick (A/B)
+#endif
+// Largest record (floats = VGPRs per lane: 2 sites x (4 covariate slots + one period block)) that is kept resident: 96, which is the
+// largest one the lean family has -- 4 + 4 covariates at 8 visits (8 + 88); the headline's 3 + 3 at 5 visits takes 56.  The record lives
+// beside the evaluation's working set in the compute waves, while the kernel's register count is set by the control wave's loop: 220 of
+// the 224 resident forms keep the parent's figures exactly (148 VGPRs / 0 bytes of scratch up to 3 + 3, 149 / 0 with four covariates on
+// a side); the four forms with 4 detection covariates at 8 visits take +2 (3 + 4) and +4 (4 + 4: 153) VGPRs over the parent's 149, still
+// without scratch or spilled VGPRs (gfx950, -Rpass-analysis=kernel-resource-usage; profiles/resident_records/resources.txt).  A form with
+// a larger record (none is instantiated today) would go on reading LDS every tick rather than risk scratch.
+#ifndef BL_RESIDENT_MAX_FLOATS
+#define BL_RESIDENT_MAX_FLOATS 96
+#endif
 #define SMALL_D_NVP(LEAN, MODEL, KS, KO) ((LEAN) && ((MODEL) == 0 || (MODEL) == 1) && (KS) + (KO) + 2 <= 8)
 #ifndef BL_GRP_FORM
 #define BL_GRP_FORM 2 // what the sampler's GRP instantiation carries: 2 = the lane-group evaluator alone, 1 = both evaluators (A/B)
@@ -245,6 +258,8 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
     // Royle-Nichols kernels keep their loops)
     constexpr bool ONE1 = LEAN && !GRP && MODEL == 0;
     const int T = ONE1 ? 1 : p.T, J = p.J;
+    // (... and, with J a compile-time fact and a record that fits the register budget, the lane's record stays in registers: BL_RESIDENT_REC)
+    constexpr bool RESIDENT = BL_RESIDENT_REC && ONE1 && LDS && JSEL > 0 && BlPairRec<KS, KO, (JSEL > 0 ? JSEL : 1)>::FLOATS <= BL_RESIDENT_MAX_FLOATS;
     const int s0 = member * p.nloc;
     int cnt = p.n_sites - s0;
     cnt = cnt < 0 ? 0 : (cnt > p.nloc ? p.nloc : cnt);
@@ -677,6 +692,15 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
         if constexpr (BL_COMPUTE_PRIO > 0 && MODEL != 1 && multi_wg) __builtin_amdgcn_s_setprio(BL_COMPUTE_PRIO);
         unsigned epoch_c = 0;  // evaluations so far = the exchange epoch of the one in flight (the control wave counts the same)
         const int lane_grp = MODEL == 1 ? bl_rn_npos(p.rn_off) : p.lane_grp; // (occu_rn: its waves' shares of the sites, rn_device.hpp)
+        // The lane's pair record is staged once and never changes: the lean plain-model forms read it into registers HERE, behind the
+        // barrier that ended the staging, and the loop's evaluation starts at the coefficient reads (BL_RESIDENT_REC).  With it go the
+        // launch constants of the lane: whether it has a pair at all, and the mask of an odd slice's dummy second site.  (The partial
+        // table's address is NOT hoisted: the publishing code forms it from compile-time offsets and the wave index, and addresses kept
+        // across this loop are what the fullest instantiations spilled and reloaded -- see the two notes in the publish path below.)
+        BlPairRec<KS, KO, (RESIDENT ? JSEL : 1)> rrec;
+        bool rvalid = false;
+        float rvmask = 0.0f;
+        if constexpr (RESIDENT) bl_load_resident_rec(tid - 64, ld, cnt, rrec, rvalid, rvmask);
         while (true) {
             // The loop control of this tick (run status, "the exchange is L2-local") is read in ONE ds_read_b64 that is issued here
             // and looked at after the evaluation: read and tested first -- two dependent LDS round trips, as it was until round 3 --
@@ -687,7 +711,8 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
 #ifdef BL_STAMPS
             const long long st_a0 = (long long)clock64();
 #endif
-            bl_phase_a<KS, KO, LDS, MODEL, CW, GRP ? BL_GRP_FORM : 0, JSEL, ONE1>(tid - 64, wave - 1, grows, ld, cnt, T, J, p.max_abundance, p.fp_mode, p.nmix_tab + s0, (MODEL == 4 && p.nmix_lds) ? 2 * ((p.nloc + 1) / 2) : p.n_stride, nsp, p.sp_lds, p.rn_off, lane_grp, p.nmix_lds);
+            if constexpr (RESIDENT) bl_phase_a_rec(wave - 1, rrec, rvalid, rvmask);
+            else bl_phase_a<KS, KO, LDS, MODEL, CW, GRP ? BL_GRP_FORM : 0, JSEL, ONE1>(tid - 64, wave - 1, grows, ld, cnt, T, J, p.max_abundance, p.fp_mode, p.nmix_tab + s0, (MODEL == 4 && p.nmix_lds) ? 2 * ((p.nloc + 1) / 2) : p.n_stride, nsp, p.sp_lds, p.rn_off, lane_grp, p.nmix_lds);
 #ifdef BL_STAMPS
             st_sub[5] += (long long)clock64() - st_a0; st_sub[4]++;
 #endif

@@ -451,18 +451,154 @@ __device__ __forceinline__ void bl_visit2(const bl_f2 (&w)[KO + 1], const float 
     for (int k = 0; k <= KO; k++) g[k] = bl_fma2(s, w[k], g[k]);
 }
 
+// A lane's PAIR record as it is held in registers: the site covariates and ONE period block of JC visits, .x / .y the two sites.
+template <int KS, int KO, int JC>
+struct BlPairRec {
+    static constexpr int XQ = (KS + 3) & ~3;
+    static constexpr int PBC = (JC * (KO + 1) + 2 + 3) & ~3;
+    static constexpr int FLOATS = 2 * (XQ + PBC); // registers a resident record takes
+    bl_f2 x[XQ], blk[PBC];
+};
+template <int N>
+__device__ __forceinline__ void bl_rec_load(const float4 *src, bl_f2 (&dst)[N])
+{
+#pragma unroll
+    for (int q = 0; q < N / 2; q++) {
+        const float4 v = src[q];
+        dst[2 * q] = bl_f2{v.x, v.y};
+        dst[2 * q + 1] = bl_f2{v.z, v.w};
+    }
+}
+// The record's two halves from LDS (ds_read_b128 at immediate offsets): the covariates, and period t's block.
+template <int KS, int KO, int JC>
+__device__ __forceinline__ void bl_rec_load_x(const float4 *rec, BlPairRec<KS, KO, JC> &r) { bl_rec_load(rec, r.x); }
+template <int KS, int KO, int JC>
+__device__ __forceinline__ void bl_rec_load_blk(const float4 *rec, int t, BlPairRec<KS, KO, JC> &r)
+{
+    bl_rec_load(rec + BlPairRec<KS, KO, JC>::XQ / 2 + t * (BlPairRec<KS, KO, JC>::PBC / 2), r.blk);
+}
+
+// The pair's site part: eta = x beta, softplus(eta), psi = sigmoid(eta)   (exact forms: once per site)
+template <int KS, int XQ>
+__device__ __forceinline__ void bl_pair_head(const bl_f2 (&x)[XQ], const float (&beta)[KS + 1], bl_f2 &eta, bl_f2 &sp, bl_f2 &psi)
+{
+    eta = bl2(beta[0]);
+#pragma unroll
+    for (int k = 0; k < KS; k++) eta = bl_fma2(x[k], bl2(beta[k + 1]), eta);
+    const bl_f2 e_eta = bl_exp2_2(__builtin_elementwise_abs(eta) * bl2(-BL_LOG2E));
+    const bl_f2 op_eta = e_eta + bl2(1.0f);
+    sp = bl_fma2(bl_log2_2(op_eta), bl2(BL_LN2), __builtin_elementwise_max(eta, bl2(0.0f)));
+    psi = bl_sel_pos_one(eta, e_eta) * bl_rcp_2(op_eta);
+}
+// The JC visits of a period block held in registers: a = ka + sum_j log sigma(u_j), kb, g = sum_j sigma(-u_j) w_j
+template <int KO, int JC, int PBC>
+__device__ __forceinline__ void bl_pair_visits(const bl_f2 (&blk)[PBC], const float (&alpha)[KO + 1], bl_f2 &a, bl_f2 &kb, bl_f2 (&g)[KO + 1])
+{
+    a = blk[JC * (KO + 1)];
+    kb = blk[JC * (KO + 1) + 1];
+#pragma unroll
+    for (int j = 0; j < JC; j++) {
+        bl_f2 w[KO + 1];
+#pragma unroll
+        for (int k = 0; k <= KO; k++) w[k] = blk[j * (KO + 1) + k];
+        bl_visit2<KO>(w, alpha, a, g);
+    }
+}
+// sum over z of one period: z=1 branch A = log psi + a ; z=0 branch B = log(1-psi) + n_det log(tiny)
+template <int KO>
+__device__ __forceinline__ void bl_pair_period_tail(bl_f2 eta, bl_f2 sp, bl_f2 psi, bl_f2 a, bl_f2 kb, const bl_f2 (&g)[KO + 1],
+                                                    bl_f2 &lsite, bl_f2 &dsum, bl_f2 (&ga2)[KO + 1])
+{
+    const bl_f2 A = eta - sp + a, B = kb - sp;
+    const bl_f2 d = eta + a - kb; // = A - B
+    const bl_f2 e_d = bl_exp2_2(__builtin_elementwise_abs(d) * bl2(-BL_LOG2E));
+    const bl_f2 op_d = e_d + bl2(1.0f);
+    lsite += bl_fma2(bl_log2_2(op_d), bl2(BL_LN2), __builtin_elementwise_max(A, B));
+    const bl_f2 q = bl_sel_pos_one(d, e_d) * bl_rcp_2(op_d); // P(z=1 | y, theta)
+    dsum += q - psi;
+#pragma unroll
+    for (int k = 0; k <= KO; k++) ga2[k] = bl_fma2(q, g[k], ga2[k]); // dummy site: g == 0
+}
+// The pair's closing sums (vmask: 0 in .y for the dummy second site of an odd slice's last pair)
+template <int KS, int XQ>
+__device__ __forceinline__ void bl_pair_close(const bl_f2 (&x)[XQ], bl_f2 vmask, bl_f2 lsite, bl_f2 dsum, bl_f2 &ll2, bl_f2 (&gb2)[KS + 1])
+{
+    ll2 = bl_fma2(lsite, vmask, ll2);
+    dsum *= vmask;
+    gb2[0] += dsum;
+#pragma unroll
+    for (int k = 0; k < KS; k++) gb2[k + 1] = bl_fma2(dsum, x[k], gb2[k + 1]);
+}
+// One pair of ONE period, evaluated from a record in registers (the order of bl_eval_sites_lds's one_pair, T = 1)
+template <int KS, int KO, int JC>
+__device__ __forceinline__ void bl_eval_pair_rec(const BlPairRec<KS, KO, JC> &r, bl_f2 vmask, const float (&beta)[KS + 1], const float (&alpha)[KO + 1],
+                                                 bl_f2 &ll2, bl_f2 (&gb2)[KS + 1], bl_f2 (&ga2)[KO + 1])
+{
+    bl_f2 eta, sp, psi;
+    bl_pair_head<KS>(r.x, beta, eta, sp, psi);
+    bl_f2 dsum = bl2(0.0f), lsite = bl2(0.0f);
+    bl_f2 g[KO + 1];
+#pragma unroll
+    for (int k = 0; k <= KO; k++) g[k] = bl2(0.0f);
+    bl_f2 a, kb;
+    bl_pair_visits<KO, JC>(r.blk, alpha, a, kb, g);
+    bl_pair_period_tail<KO>(eta, sp, psi, a, kb, g, lsite, dsum, ga2);
+    bl_pair_close<KS>(r.x, vmask, lsite, dsum, ll2, gb2);
+}
+// The evaluators' closing fold of the two sites of a lane into its accumulators
+template <int KS, int KO>
+__device__ __forceinline__ void bl_pair_fold(bl_f2 ll2, const bl_f2 (&gb2)[KS + 1], const bl_f2 (&ga2)[KO + 1], float &ll, float (&gb)[KS + 1], float (&ga)[KO + 1])
+{
+    ll += ll2.x + ll2.y;
+#pragma unroll
+    for (int k = 0; k <= KS; k++) gb[k] += gb2[k].x + gb2[k].y;
+#pragma unroll
+    for (int k = 0; k <= KO; k++) ga[k] += ga2[k].x + ga2[k].y;
+}
+
+// The sampler's lean instantiations (one period, at most one pair per lane, JC visits) with the lane's record RESIDENT in registers:
+// loaded once per launch (bl_load_resident_rec), evaluated every tick without touching the staged data.  A lane without a pair
+// (valid == false) contributes nothing: the accumulators keep their identity, exactly as in bl_eval_sites_lds.
+template <int KS, int KO, int JC>
+__device__ __forceinline__ void bl_load_resident_rec(int ct, int pstride, int cnt, BlPairRec<KS, KO, JC> &r, bool &valid, float &vmask_y)
+{
+    const int npairs = (cnt + 1) >> 1;
+    valid = ct < npairs;
+    // (a lane without a pair reads the slice's last record, a workgroup without sites the first record's place: inside the staged region)
+    const int m = valid ? ct : (npairs > 0 ? npairs - 1 : 0);
+    const float4 *rec = reinterpret_cast<const float4 *>(bl_lds_f(BL_OFF_DATA) + (size_t)m * pstride);
+    bl_rec_load_x(rec, r);
+    bl_rec_load_blk(rec, 0, r);
+    vmask_y = (2 * m + 1 < cnt) ? 1.0f : 0.0f; // odd slice: the last pair's second site is a dummy
+}
+template <int KS, int KO, int JC>
+__device__ __forceinline__ void bl_eval_sites_rec(const BlPairRec<KS, KO, JC> &r, bool valid, float vmask_y,
+                                                  const float (&beta)[KS + 1], const float (&alpha)[KO + 1],
+                                                  float &ll, float (&gb)[KS + 1], float (&ga)[KO + 1])
+{
+    bl_f2 ll2 = bl2(0.0f), gb2[KS + 1], ga2[KO + 1];
+#pragma unroll
+    for (int k = 0; k <= KS; k++) gb2[k] = bl2(0.0f);
+#pragma unroll
+    for (int k = 0; k <= KO; k++) ga2[k] = bl2(0.0f);
+    if (valid) bl_eval_pair_rec<KS, KO, JC>(r, bl_f2{1.0f, vmask_y}, beta, alpha, ll2, gb2, ga2);
+    bl_pair_fold<KS, KO>(ll2, gb2, ga2, ll, gb, ga);
+}
+
 // Accumulates, over this thread's site PAIRS m = ct, ct+CT, ... (CT compute threads):
 //   ll += sum_t l_it ,  gb[k] += d ll / d beta_k ,  ga[k] += d ll / d alpha_k
 // LDS pair records (element e of the two sites adjacent); JC > 0: J == JC at compile time -> the
 // whole period block is read with ds_read_b128 at immediate offsets and the visits are unrolled
 // (their exp/log/rcp chains interleave).  JC == 0: runtime J.
 // ONE1 (the sampler's lean instantiations): one period and at most one pair per lane -- no loops, straight-line code
+// The arithmetic is the bl_pair_* pieces above; this form reads the record from LDS at every call.
 template <int KS, int KO, int JC, int CT, bool ONE1 = false>
 __device__ __forceinline__ void bl_eval_sites_lds(int ct, int pstride, int cnt, int T, int J,
                                                   const float (&beta)[KS + 1], const float (&alpha)[KO + 1],
                                                   float &ll, float (&gb)[KS + 1], float (&ga)[KO + 1], int data_off = 0)
 {
-    constexpr int XQ = (KS + 3) & ~3;
+    typedef BlPairRec<KS, KO, (JC > 0 ? JC : 1)> Rec;
+    constexpr int XQ = Rec::XQ;
     const int Jn = JC > 0 ? JC : J;
     const int pb = bl_period_block(Jn, KO);
     const float *data = bl_lds_f(BL_OFF_DATA) + data_off; // (data_off: the records of one species of a joint-species dataset)
@@ -475,21 +611,10 @@ __device__ __forceinline__ void bl_eval_sites_lds(int ct, int pstride, int cnt, 
     auto one_pair = [&](int m) {
         const float4 *rec = reinterpret_cast<const float4 *>(data + (size_t)m * pstride);
         const bl_f2 vmask = bl_f2{1.0f, (2 * m + 1 < cnt) ? 1.0f : 0.0f}; // odd slice: the last pair's second site is a dummy
-        bl_f2 x[XQ];
-#pragma unroll
-        for (int q = 0; q < XQ / 2; q++) {
-            const float4 v = rec[q];
-            x[2 * q] = bl_f2{v.x, v.y};
-            x[2 * q + 1] = bl_f2{v.z, v.w};
-        }
-        bl_f2 eta = bl2(beta[0]);
-#pragma unroll
-        for (int k = 0; k < KS; k++) eta = bl_fma2(x[k], bl2(beta[k + 1]), eta);
-        // softplus(eta), psi = sigmoid(eta)   (exact forms: once per site)
-        const bl_f2 e_eta = bl_exp2_2(__builtin_elementwise_abs(eta) * bl2(-BL_LOG2E));
-        const bl_f2 op_eta = e_eta + bl2(1.0f);
-        const bl_f2 sp = bl_fma2(bl_log2_2(op_eta), bl2(BL_LN2), __builtin_elementwise_max(eta, bl2(0.0f)));
-        const bl_f2 psi = bl_sel_pos_one(eta, e_eta) * bl_rcp_2(op_eta);
+        Rec r;
+        bl_rec_load_x(rec, r);
+        bl_f2 eta, sp, psi;
+        bl_pair_head<KS>(r.x, beta, eta, sp, psi);
         bl_f2 dsum = bl2(0.0f), lsite = bl2(0.0f);
         auto one_period = [&](int t) {
             bl_f2 g[KO + 1];
@@ -497,24 +622,8 @@ __device__ __forceinline__ void bl_eval_sites_lds(int ct, int pstride, int cnt, 
             for (int k = 0; k <= KO; k++) g[k] = bl2(0.0f);
             bl_f2 a, kb;
             if constexpr (JC > 0) {
-                constexpr int PBC = (JC * (KO + 1) + 2 + 3) & ~3;
-                const float4 *pq = rec + XQ / 2 + t * (PBC / 2);
-                bl_f2 blk[PBC];
-#pragma unroll
-                for (int q = 0; q < PBC / 2; q++) {
-                    const float4 v = pq[q];
-                    blk[2 * q] = bl_f2{v.x, v.y};
-                    blk[2 * q + 1] = bl_f2{v.z, v.w};
-                }
-                a = blk[JC * (KO + 1)];
-                kb = blk[JC * (KO + 1) + 1];
-#pragma unroll
-                for (int j = 0; j < JC; j++) {
-                    bl_f2 w[KO + 1];
-#pragma unroll
-                    for (int k = 0; k <= KO; k++) w[k] = blk[j * (KO + 1) + k];
-                    bl_visit2<KO>(w, alpha, a, g);
-                }
+                bl_rec_load_blk(rec, t, r);
+                bl_pair_visits<KO, JC>(r.blk, alpha, a, kb, g);
             } else {
                 const float2 *pp = reinterpret_cast<const float2 *>(data + (size_t)m * pstride) + XQ + t * pb;
                 const float2 a_ = pp[Jn * (KO + 1)], kb_ = pp[Jn * (KO + 1) + 1];
@@ -531,32 +640,15 @@ __device__ __forceinline__ void bl_eval_sites_lds(int ct, int pstride, int cnt, 
                     bl_visit2<KO>(w, alpha, a, g);
                 }
             }
-            // sum over z: z=1 branch A = log psi + a ; z=0 branch B = log(1-psi) + n_det log(tiny)
-            const bl_f2 A = eta - sp + a, B = kb - sp;
-            const bl_f2 d = eta + a - kb; // = A - B
-            const bl_f2 e_d = bl_exp2_2(__builtin_elementwise_abs(d) * bl2(-BL_LOG2E));
-            const bl_f2 op_d = e_d + bl2(1.0f);
-            lsite += bl_fma2(bl_log2_2(op_d), bl2(BL_LN2), __builtin_elementwise_max(A, B));
-            const bl_f2 q = bl_sel_pos_one(d, e_d) * bl_rcp_2(op_d); // P(z=1 | y, theta)
-            dsum += q - psi;
-#pragma unroll
-            for (int k = 0; k <= KO; k++) ga2[k] = bl_fma2(q, g[k], ga2[k]); // dummy site: g == 0
+            bl_pair_period_tail<KO>(eta, sp, psi, a, kb, g, lsite, dsum, ga2);
         };
         if constexpr (ONE1) one_period(0); // (one period: no loop)
         else for (int t = 0; t < T; t++) one_period(t);
-        ll2 = bl_fma2(lsite, vmask, ll2);
-        dsum *= vmask;
-        gb2[0] += dsum;
-#pragma unroll
-        for (int k = 0; k < KS; k++) gb2[k + 1] = bl_fma2(dsum, x[k], gb2[k + 1]);
+        bl_pair_close<KS>(r.x, vmask, lsite, dsum, ll2, gb2);
     };
     if constexpr (ONE1) { if (ct < npairs) one_pair(ct); } // (at most one pair per lane: no loop)
     else for (int m = ct; m < npairs; m += CT) one_pair(m);
-    ll += ll2.x + ll2.y;
-#pragma unroll
-    for (int k = 0; k <= KS; k++) gb[k] += gb2[k].x + gb2[k].y;
-#pragma unroll
-    for (int k = 0; k <= KO; k++) ga[k] += ga2[k].x + ga2[k].y;
+    bl_pair_fold<KS, KO>(ll2, gb2, ga2, ll, gb, ga);
 }
 
 // Same arithmetic straight from the HBM rows (slice too large for LDS); grows is already offset to
@@ -1429,4 +1521,20 @@ __device__ __forceinline__ void bl_phase_a(int ct, int cwave, const float *__res
         bl_wave_partials_to_lds<KS, KO>(cwave, ll, gb, ga, 0.0f, row_stride, sp * BL_SP_PART(KS, KO));
     }
     }
+}
+
+// Phase A of the sampler's lean plain-model kernels whose lanes keep their record in registers (nuts_kernel.hpp: BL_RESIDENT_REC):
+// bl_phase_a's plain-model branch for one species, with the evaluation fed from the resident record instead of LDS.
+template <int KS, int KO, int JC>
+__device__ __forceinline__ void bl_phase_a_rec(int cwave, const BlPairRec<KS, KO, JC> &rec, bool valid, float vmask_y)
+{
+    float beta[KS + 1], alpha[KO + 1];
+    bl_load_coefs<KS, KO>(beta, alpha, 0);
+    float ll = -0.0f, gb[KS + 1], ga[KO + 1]; // (-0.0f: see bl_phase_a)
+#pragma unroll
+    for (int k = 0; k <= KS; k++) gb[k] = -0.0f;
+#pragma unroll
+    for (int k = 0; k <= KO; k++) ga[k] = -0.0f;
+    bl_eval_sites_rec<KS, KO, JC>(rec, valid, vmask_y, beta, alpha, ll, gb, ga);
+    bl_wave_partials_to_lds<KS, KO>(cwave, ll, gb, ga, 0.0f, BL_PART_STRIDE, 0);
 }
