@@ -61,8 +61,8 @@ __global__ void bl_abundance_posterior_kernel(const BlAbundPostParams p)
         const float *__restrict__ al = th + p.o_al;
         double etad = (double)th[0];
         for (int k = 0; k < p.Ks; k++) etad = fma((double)rows[(size_t)k * ns + i], (double)th[k + 1], etad);
-        if (p.o_u >= 0) etad += (double)th[p.o_u + i];
-        const float vi = p.o_v >= 0 ? th[p.o_v + i] : 0.0f;
+        if (p.c.o_u >= 0) etad += (double)th[p.c.o_u + i];
+        const float vi = p.c.o_v >= 0 ? th[p.c.o_v + i] : 0.0f;
         const float lam = bl_exp(fminf((float)etad, 80.0f)); // (the stopping rule's only: n >= lambda)
         // what every l_n carries besides n eta - lgamma(n + 1): -lambda (nmixture), -log Z (occu_rn; Z over 0 .. K)
         double shift;
@@ -79,8 +79,8 @@ __global__ void bl_abundance_posterior_kernel(const BlAbundPostParams p)
                 if (pn > -AP_CUT) sz += exp(pn);
             }
             shift = -(m0 + log(sz));
-            if (p.o_fp >= 0) {
-                const float phi = th[p.o_fp];
+            if (p.c.o_fp >= 0) {
+                const float phi = th[p.c.o_fp];
                 post_sig(phi, fpr, gq);
                 lgqd = -ap_softplus((double)phi);
                 lgq = (float)lgqd;
@@ -92,7 +92,7 @@ __global__ void bl_abundance_posterior_kernel(const BlAbundPostParams p)
                 const int v = t * J + j;
                 const size_t r = (size_t)(p.r0 + v * p.vw) * ns + i;
                 float re = vi;
-                if (p.o_e >= 0) re += th[(size_t)p.o_e + (size_t)i * T * J + v];
+                if (p.c.o_e >= 0) re += th[(size_t)p.c.o_e + (size_t)i * T * J + v];
                 c = rows[r];
                 float u = c * al[0];
                 for (int k = 1; k <= Ko; k++) u = fmaf(rows[r + (size_t)k * ns], al[k], u);
@@ -103,7 +103,7 @@ __global__ void bl_abundance_posterior_kernel(const BlAbundPostParams p)
                 const int v = t * J + j;
                 const size_t r = (size_t)(p.r0 + v * p.vw) * ns + i;
                 double u = (double)al[0] + (double)vi;
-                if (p.o_e >= 0) u += (double)th[(size_t)p.o_e + (size_t)i * T * J + v];
+                if (p.c.o_e >= 0) u += (double)th[(size_t)p.c.o_e + (size_t)i * T * J + v];
                 c = rows[NMIX ? r + ns : r];
                 const double sg = NMIX ? 1.0 : (double)c; // (c w_k) c = w_k
                 for (int k = 0; k < Ko; k++) u = fma((double)rows[r + (size_t)((NMIX ? 2 : 1) + k) * ns] * sg, (double)al[k + 1], u);
@@ -184,7 +184,7 @@ __global__ void bl_abundance_posterior_kernel(const BlAbundPostParams p)
             if (p.log_lik) p.log_lik[o] = l;
             if (!p.n_mean && !p.occ_prob && !p.n_draw) continue;
             // ---- pass 2: the first moment, the mass at 0, the draw by inversion ----
-            BlPredRng rng(p.seed, ((unsigned long long)d * T + t) * N + i);
+            BlPredRng rng = bl_cell_rng(p.seed, d, T, t, N, i);
             const double target = (double)rng.uniform() * S;
             double S1 = 0.0, cum = 0.0, w0 = 0.0;
             int draw = -1, last = lo;

@@ -8,6 +8,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "draw_coords.hpp"
+
 struct BlAbundPostParams {
     const float *rows;        // [n_rows][ns], site-fastest; rows 0 .. Ks - 1 = the site covariates
     const float *tab;         // nmixture: [T][K + 1][ns]; NULL for occu_rn
@@ -17,8 +19,7 @@ struct BlAbundPostParams {
     int nmix;                 // 0 = occu_rn, 1 = nmixture
     int K;                    // max_abundance (< 128: the lgamma table)
     int o_al;                 // where the Ko + 1 detection coefficients start in a draw
-    int o_fp;                 // occu_rn: phi = logit(false-positive rate) in a draw; -1 = no rate
-    int o_u, o_v, o_e;        // random effects in a draw (external order: [N], [N], [N][T][J]); -1 = absent
+    BlDrawCoords c;           // occu_rn: the false-positive rate (phi = logit(rate); the kernel asks o_fp alone), the random effects
     const float *draws;       // [n_draws][D], device
     int n0, n1;               // the draws of this launch; outputs are indexed from n0
     unsigned long long seed;

@@ -19,7 +19,7 @@
 #include "logp_kernel.hpp"
 #include "re_kernel.hpp"
 #include "nuts_kernel.hpp"
-#include "pred_rng.hpp"
+#include "predict.hpp"
 #include "site_posterior.hpp"
 #include "abundance_posterior.hpp"
 #include "path_posterior.hpp"
@@ -333,6 +333,24 @@ static bool re_kind_in(const bl_dataset *ds, std::initializer_list<int> kinds)
     return ds->model == 6 && std::find(kinds.begin(), kinds.end(), ds->re.kind) != kinds.end();
 }
 
+// The plain model whose branch of a predictive kernel the handle runs: a random-effects handle runs its kind's.
+static int branch_model(const bl_dataset *ds)
+{
+    static const int of_kind[] = {0, 0, 2, 4, 1, 1, 3, 3, 0};
+    return ds->model == 6 && ds->re.kind >= 0 && ds->re.kind <= 8 ? of_kind[ds->re.kind] : ds->model;
+}
+// A handle's draw layout as the post-fit kernels are told it: o_fp is the false-positive coordinate if the handle has one (behind the
+// coefficients with random effects, else the last one) and fp_mode its mode, else -1 and 0; the effects' offsets, -1 = absent.
+static BlDrawCoords draw_coords(const bl_dataset *ds)
+{
+    const bool re = ds->model == 6;
+    BlDrawCoords c;
+    c.fp_mode = re ? ds->re.fp_mode : ds->fp_mode;
+    c.o_fp = c.fp_mode ? (re ? ds->re.o_fp : ds->D - 1) : -1;
+    c.o_u = re ? ds->re.o_u : -1; c.o_v = re ? ds->re.o_v : -1; c.o_e = re ? ds->re.o_e : -1;
+    return c;
+}
+
 // What every per-draw entry checks before it touches the device.  `serves`: does the entry serve this handle; `built`: what it does serve.
 static int per_draw_front(const char *entry, const bl_dataset *ds, int n_draws, const float *draws, bool any_output,
                           bool (*serves)(const bl_dataset *), const char *built)
@@ -387,68 +405,27 @@ static int run_over_draws(const bl_dataset *ds, int n_draws, const float *draws,
     }
     return BL_OK;
 }
+// The usual launch: the chunk's draws and bounds into the entry's kernel parameters, then its launcher.
+template <size_t K, class Params>
+static int run_over_draws(const bl_dataset *ds, int n_draws, const float *draws, size_t chunk_bytes, const DrawOut (&outs)[K], Params &p,
+                          int (*launcher)(const Params *, int, hipStream_t))
+{
+    return run_over_draws(ds, n_draws, draws, chunk_bytes, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
+        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
+        return (hipError_t)launcher(&p, grid_y, nullptr);
+    });
+}
 
 // ------------------------------------------------------------------ posterior predictive ----
-// (the generator, one per (draw, period, site): pred_rng.hpp)
-// occu (occu.py:207-241 with obs=None):  z ~ Bernoulli(psi),  y_j ~ Bernoulli(z * p_j)
-// occu_rn (occu_rn.py:192-221):          N ~ Categorical(Poisson(lambda) pmf on 0..K),  y_j ~ Bernoulli(1 - (1 - r_j)^N)
-__global__ void bl_predict_kernel(const float *__restrict__ rows, const float *__restrict__ wraw, int n_stride, int N, int T, int J,
-                                  int Ks, int Ko, int D, const float *__restrict__ draws, int n0, int n1,
-                                  unsigned long long seed, int model, int max_abundance, int fp_mode,
-                                  unsigned char *__restrict__ latent, unsigned char *__restrict__ y, int o_u, int o_v, int o_e, int o_fp)
+// Kernels: predict.hip (bl_predict, bl_predict_counts, bl_predict_scores, bl_deterministic).  What they read of the handle, once the raw
+// rows they need are up:
+static BlPredictParams predict_params(const bl_dataset *ds, uint64_t seed)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    float x[BL_MAX_COVS];
-    for (int k = 0; k < Ks; k++) x[k] = rows[(size_t)k * n_stride + i];
-    for (int n = n0 + blockIdx.y; n < n1; n += gridDim.y) {
-        const float *th = draws + (size_t)n * D;
-        const float *al = th + Ks + 1;
-        float eta = th[0];
-        for (int k = 0; k < Ks; k++) eta = fmaf(x[k], th[k + 1], eta);
-        if (o_u >= 0) eta += th[o_u + i]; // random effects (model 6; offsets into a draw, -1 = absent): occu.py:198-202, 221-228
-        // false-positive rate (model 2): acts on every site ("constant") or on unoccupied ones only
-        // (o_fp: where phi = logit(rate) sits in a draw -- the last coordinate, or right behind the coefficients with random effects)
-        const float fpr = (model == 2 || (model == 1 && fp_mode == BL_FP_CONSTANT && o_fp >= 0)) ? 1.0f / (1.0f + __expf(-th[o_fp])) : 0.0f;
-        const float f_c = fp_mode == BL_FP_CONSTANT ? fpr : 0.0f, f_u = fp_mode == BL_FP_UNOCCUPIED ? fpr : 0.0f;
-        for (int t = 0; t < T; t++) {
-            BlPredRng rng(seed, ((unsigned long long)n * T + t) * N + i);
-            int zn;
-            if (model == 1) {
-                // inversion over the (renormalised) truncated Poisson pmf, float64 recursion p_n = p_{n-1} lambda / n
-                const double lam = exp((double)eta);
-                double p = exp(-lam), tot = 0.0;
-                for (int m = 0; m <= max_abundance; m++) { tot += p; p *= lam / (double)(m + 1); }
-                const double target = (double)rng.uniform() * tot;
-                p = exp(-lam);
-                double cum = 0.0;
-                zn = max_abundance;
-                for (int m = 0; m <= max_abundance; m++) {
-                    cum += p;
-                    if (target < cum) { zn = m; break; }
-                    p *= lam / (double)(m + 1);
-                }
-            } else {
-                const float psi = 1.0f / (1.0f + __expf(-eta));
-                zn = rng.uniform() < psi ? 1 : 0;
-            }
-            if (latent) latent[((size_t)(n - n0) * T + t) * N + i] = (unsigned char)zn;
-            if (!y) continue;
-            for (int j = 0; j < J; j++) {
-                const int v = t * J + j;
-                float nu = al[0];
-                for (int k = 0; k < Ko; k++) nu = fmaf(wraw[((size_t)v * Ko + k) * n_stride + i], al[k + 1], nu);
-                if (o_v >= 0) nu += th[o_v + i];
-                if (o_e >= 0) nu += th[o_e + (size_t)i * T * J + v];
-                const float r = 1.0f / (1.0f + __expf(-nu));
-                float pd = model == 1 ? 1.0f - __powf(1.0f - r, (float)zn) : (float)zn * r;
-                if (model == 2) pd = 1.0f - (1.0f - pd) * (1.0f - f_c) * (1.0f - (zn ? 0.0f : f_u));
-                if (model == 1) pd = 1.0f - (1.0f - pd) * (1.0f - fpr); // (Royle-Nichols with a false-positive rate: occu_rn.py:214-221; fpr = 0 without)
-                const float u = rng.uniform();
-                y[(((size_t)(n - n0) * J + j) * T + t) * N + i] = (u < pd) ? 1 : 0;
-            }
-        }
-    }
+    BlPredictParams p{};
+    p.rows = ds->d_rows; p.wraw = ds->d_wraw; p.dur = ds->d_dur; p.ns = ds->n_stride;
+    p.N = ds->dims.n_sites; p.T = ds->dims.n_periods; p.J = ds->dims.n_replicates; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = ds->D;
+    p.model = branch_model(ds); p.K = ds->max_abundance; p.c = draw_coords(ds); p.seed = (unsigned long long)seed;
+    return p;
 }
 
 extern "C" int bl_predict(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, uint8_t *latent, uint8_t *y)
@@ -459,20 +436,10 @@ extern "C" int bl_predict(bl_dataset *ds, int n_draws, const float *draws, uint6
                             },
                             "occu, occu_fp, occu_re and occu_rn; the count models use bl_predict_counts, occu_cs bl_predict_scores");
     if (rc || (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
-    const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates, D = ds->D;
-    unsigned char *d_lat, *d_y;
-    const DrawOut outs[] = {{latent, (size_t)T * N, (void **)&d_lat, false}, {y, (size_t)J * T * N, (void **)&d_y, false}};
-    const size_t largest = (size_t)T * N * (y ? (size_t)J : 1); // bytes of the larger output of one draw
-    return run_over_draws(ds, n_draws, draws, largest, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
-        hipLaunchKernelGGL(bl_predict_kernel, dim3((N + 255) / 256, grid_y), dim3(256), 0, nullptr, ds->d_rows, ds->d_wraw, ds->n_stride,
-                           N, T, J, ds->Ks, ds->Ko, D, d_draws, n0, n1, (unsigned long long)seed,
-                           // random-effects handles: Royle-Nichols (kind 4) / false positives (kind 2) run those branches with the effects
-                           re_kind_in(ds, {4, 5}) ? 1 : (re_kind_in(ds, {2}) ? 2 : ds->model),
-                           ds->max_abundance, re_kind_in(ds, {2, 5}) ? ds->re.fp_mode : ds->fp_mode, d_lat, d_y,
-                           ds->model == 6 ? ds->re.o_u : -1, ds->model == 6 ? ds->re.o_v : -1, ds->model == 6 ? ds->re.o_e : -1,
-                           ds->model == 6 ? (re_kind_in(ds, {2, 5}) ? ds->re.o_fp : -1) : D - 1);
-        return hipGetLastError();
-    });
+    BlPredictParams p = predict_params(ds, seed);
+    const size_t cells = (size_t)p.T * p.N; // per draw
+    const DrawOut outs[] = {{latent, cells, (void **)&p.latent, false}, {y, cells * p.J, (void **)&p.y, false}};
+    return run_over_draws(ds, n_draws, draws, cells * (y ? (size_t)p.J : 1), outs, p, bl_launch_predict);
 }
 
 // ---- conditional occupancy: P(z | data), the site-period log-likelihood and a draw of z, per posterior draw ----
@@ -487,7 +454,7 @@ extern "C" int bl_site_posterior(bl_dataset *ds, int n_draws, const float *draws
     const int N = ds->dims.n_sites, T = ds->dims.n_periods, D = ds->D;
     BlSitePostParams p{};
     p.ns = ds->n_stride; p.N = N; p.T = T; p.Ks = ds->Ks; p.D = D; p.seed = (unsigned long long)seed;
-    p.o_u = p.o_v = p.o_e = p.o_fp = -1; p.r_per = p.o_x = 0;
+    p.c = draw_coords(ds);
     if (ds->model == 6 && ds->re.kind == 8) { // occu_comb: its own rows (bl_dataset_create_comb)
         const BlReModel &m = ds->re;
         const BlCombModel &cm = ds->comb;
@@ -500,21 +467,12 @@ extern "C" int bl_site_posterior(bl_dataset *ds, int n_draws, const float *draws
         p.rows = ds->d_rows;
         p.a = BlSitePostBlock{ds->KS, ds->dims.n_replicates, Ko, ds->KO + 1, ds->Ks + 1};
         p.b = BlSitePostBlock{0, 0, 0, 1, 0};
-        if (ds->model == 2) { p.fp_mode = ds->fp_mode; p.o_fp = D - 1; }
-        if (ds->model == 6) {
-            const BlReModel &m = ds->re;
-            if (m.kind == 2) { p.fp_mode = m.fp_mode; p.o_fp = m.o_fp; }
-            p.o_u = m.o_u; p.o_v = m.o_v; p.o_e = m.o_e;
-        }
     }
     const size_t cells = (size_t)T * N; // per draw; the larger outputs are 4 bytes a cell
     const DrawOut outs[] = {{log_lik, cells * 4, (void **)&p.log_lik, false},
                             {z_prob, cells * 4, (void **)&p.z_prob, false},
                             {z, cells, (void **)&p.z, false}};
-    return run_over_draws(ds, n_draws, draws, cells * 4, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
-        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
-        return (hipError_t)bl_launch_site_posterior(&p, grid_y, nullptr);
-    });
+    return run_over_draws(ds, n_draws, draws, cells * 4, outs, p, bl_launch_site_posterior);
 }
 
 // ---- conditional abundance: P(N | data), the site-period log-likelihood and a draw of N, per posterior draw ----
@@ -532,26 +490,18 @@ extern "C" int bl_abundance_posterior(bl_dataset *ds, int n_draws, const float *
     BlAbundPostParams p{};
     p.rows = ds->d_rows; p.ns = ds->n_stride; p.N = N; p.T = T; p.J = J; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = D;
     p.r0 = ds->KS; p.vw = ds->KO + 2; p.o_al = ds->Ks + 1; p.seed = (unsigned long long)seed;
-    p.o_fp = p.o_u = p.o_v = p.o_e = -1;
+    p.c = draw_coords(ds);
     p.nmix = (ds->model == 4 || (ds->model == 6 && ds->re.kind == 3)) ? 1 : 0;
     p.K = ds->model == 6 ? ds->re.max_abundance : ds->max_abundance;
     p.tab = p.nmix ? ds->d_tab : nullptr;
     p.r_ymax = ds->KS + T * J * p.vw;
-    if (ds->model == 6) {
-        const BlReModel &m = ds->re;
-        if (m.kind == 5) p.o_fp = m.o_fp;
-        p.o_u = m.o_u; p.o_v = m.o_v; p.o_e = m.o_e;
-    }
     if (p.K < 1 || p.K >= BL_RN_NB || (p.nmix && !p.tab)) return bl_fail(BL_ERR_INVALID, "bl_abundance_posterior: the handle carries no abundance table");
     const size_t cells = (size_t)T * N; // per draw; every output is 4 bytes a cell
     const DrawOut outs[] = {{log_lik, cells * 4, (void **)&p.log_lik, false},
                             {n_mean, cells * 4, (void **)&p.n_mean, false},
                             {occ_prob, cells * 4, (void **)&p.occ_prob, false},
                             {n_draw, cells * 4, (void **)&p.n_draw, false}};
-    return run_over_draws(ds, n_draws, draws, cells * 4, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
-        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
-        return (hipError_t)bl_launch_abundance_posterior(&p, grid_y, nullptr);
-    });
+    return run_over_draws(ds, n_draws, draws, cells * 4, outs, p, bl_launch_abundance_posterior);
 }
 
 // ---- conditional dynamics: the smoothed P(z_t | all seasons' data), the transitions' pairwise terms, the site log-likelihood and a
@@ -576,10 +526,7 @@ extern "C" int bl_path_posterior(bl_dataset *ds, int n_draws, const float *draws
                             {col_prob, pairs * 4, (void **)&p.col_prob, false},   // (T = 1: empty, skipped)
                             {ext_prob, pairs * 4, (void **)&p.ext_prob, false},
                             {z, cells, (void **)&p.z, false}};
-    return run_over_draws(ds, n_draws, draws, cells * 4, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
-        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
-        return (hipError_t)bl_launch_path_posterior(&p, grid_y, nullptr);
-    });
+    return run_over_draws(ds, n_draws, draws, cells * 4, outs, p, bl_launch_path_posterior);
 }
 
 // ---- conditional scores: P(z | data) and P(f_j | data) of the continuous-score model, the cell log-likelihood and a joint draw of
@@ -605,10 +552,7 @@ extern "C" int bl_score_posterior(bl_dataset *ds, int n_draws, const float *draw
                             {z, cells, (void **)&p.z, false},
                             {f_prob, visits * 4, (void **)&p.f_prob, false},
                             {f, visits, (void **)&p.f, false}};
-    return run_over_draws(ds, n_draws, draws, (f_prob || f ? visits : cells) * 4, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
-        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
-        return (hipError_t)bl_launch_score_posterior(&p, grid_y, nullptr);
-    });
+    return run_over_draws(ds, n_draws, draws, (f_prob || f ? visits : cells) * 4, outs, p, bl_launch_score_posterior);
 }
 
 // ---- conditional counts: P(z | data) of the count-detection model, the cell log-likelihood, and how many of a visit's counted
@@ -630,79 +574,26 @@ extern "C" int bl_count_posterior(bl_dataset *ds, int n_draws, const float *draw
     p.rows = ds->d_rows; p.ccell = ds->d_ccell;
     p.ns = ds->n_stride; p.N = N; p.T = T; p.J = J; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = ds->D;
     p.r0 = ds->KS; p.vw = ds->KO + 2; p.r_sum = ds->KS + T * J * p.vw; p.seed = (unsigned long long)seed;
-    p.fp_mode = ds->fp_mode;
-    p.o_fp = p.o_u = p.o_v = p.o_e = -1;
-    if (ds->model == 6) {
-        const BlReModel &m = ds->re;
-        p.o_fp = m.o_fp; p.o_u = m.o_u; p.o_v = m.o_v; p.o_e = m.o_e;
-    } else if (ds->fp_mode) {
-        p.o_fp = ds->D - 1; // the trailing coordinate
-    }
+    p.c = draw_coords(ds);
     const size_t cells = (size_t)T * N, visits = (size_t)J * cells; // per draw
     const DrawOut outs[] = {{log_lik, cells * 4, (void **)&p.log_lik, false},
                             {z_prob, cells * 4, (void **)&p.z_prob, false},
                             {z, cells, (void **)&p.z, false},
                             {true_mean, visits * 4, (void **)&p.true_mean, false},
                             {true_count, visits * 4, (void **)&p.true_count, false}};
-    return run_over_draws(ds, n_draws, draws, (true_mean || true_count ? visits : cells) * 4, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
-        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
-        return (hipError_t)bl_launch_count_posterior(&p, grid_y, nullptr);
-    });
+    return run_over_draws(ds, n_draws, draws, (true_mean || true_count ? visits : cells) * 4, outs, p, bl_launch_count_posterior);
 }
 
 // ---- predictive scores of the continuous-score model (occu_cs.py:196-232 with obs=None) ----
-// z ~ Bernoulli(psi);  f_j ~ Bernoulli(z p_j);  s_j ~ Normal(mu_f, sigma_f)   (draw = [beta, alpha, mu0, log(mu1 - mu0), log sigma0, log sigma1])
-__global__ void bl_predict_scores_kernel(const float *__restrict__ rows, const float *__restrict__ wraw, int n_stride, int N, int T, int J,
-                                         int Ks, int Ko, int D, const float *__restrict__ draws, int n0, int n1, unsigned long long seed,
-                                         unsigned char *__restrict__ latent, unsigned char *__restrict__ f_out, float *__restrict__ s_out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    float x[BL_MAX_COVS];
-    for (int k = 0; k < Ks; k++) x[k] = rows[(size_t)k * n_stride + i];
-    for (int n = n0 + blockIdx.y; n < n1; n += gridDim.y) {
-        const float *th = draws + (size_t)n * D, *al = th + Ks + 1, *ex = th + Ks + Ko + 2;
-        const float mu0 = ex[0], mu1 = ex[0] + __expf(ex[1]), sg0 = __expf(ex[2]), sg1 = __expf(ex[3]);
-        float eta = th[0];
-        for (int k = 0; k < Ks; k++) eta = fmaf(x[k], th[k + 1], eta);
-        const float psi = 1.0f / (1.0f + __expf(-eta));
-        for (int t = 0; t < T; t++) {
-            BlPredRng rng(seed, ((unsigned long long)n * T + t) * N + i);
-            const int zn = rng.uniform() < psi ? 1 : 0;
-            if (latent) latent[((size_t)(n - n0) * T + t) * N + i] = (unsigned char)zn;
-            for (int j = 0; j < J; j++) {
-                const int v = t * J + j;
-                float nu = al[0];
-                for (int k = 0; k < Ko; k++) nu = fmaf(wraw[((size_t)v * Ko + k) * n_stride + i], al[k + 1], nu);
-                const int fn = rng.uniform() < (float)zn / (1.0f + __expf(-nu)) ? 1 : 0;
-                // Box-Muller, one normal per replicate
-                const float u1 = fmaxf(rng.uniform(), 5.9604645e-08f), u2 = rng.uniform();
-                const float g = sqrtf(-2.0f * __logf(u1)) * __cosf(6.2831853f * u2);
-                const size_t o = (((size_t)(n - n0) * J + j) * T + t) * N + i;
-                if (f_out) f_out[o] = (unsigned char)fn;
-                if (s_out) s_out[o] = fn ? fmaf(sg1, g, mu1) : fmaf(sg0, g, mu0);
-            }
-        }
-    }
-}
-
 extern "C" int bl_predict_scores(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, uint8_t *latent, uint8_t *f, float *s)
 {
     int rc = per_draw_front("bl_predict_scores", ds, n_draws, draws, latent || f || s,
                             [](const bl_dataset *d) { return re_kind_in(d, {1}); }, "an occu_cs dataset is required");
     if (rc || (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
-    const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates, D = ds->D;
-    unsigned char *d_lat, *d_f;
-    float *d_s;
-    const size_t visits = (size_t)J * T * N; // per draw
-    const DrawOut outs[] = {{latent, (size_t)T * N, (void **)&d_lat, false},
-                            {f, visits, (void **)&d_f, false},
-                            {s, visits * 4, (void **)&d_s, false}};
-    return run_over_draws(ds, n_draws, draws, visits * 4, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
-        hipLaunchKernelGGL(bl_predict_scores_kernel, dim3((N + 255) / 256, grid_y), dim3(256), 0, nullptr, ds->d_rows, ds->d_wraw,
-                           ds->n_stride, N, T, J, ds->Ks, ds->Ko, D, d_draws, n0, n1, (unsigned long long)seed, d_lat, d_f, d_s);
-        return hipGetLastError();
-    });
+    BlPredictParams p = predict_params(ds, seed);
+    const size_t cells = (size_t)p.T * p.N, visits = cells * p.J; // per draw
+    const DrawOut outs[] = {{latent, cells, (void **)&p.latent, false}, {f, visits, (void **)&p.f, false}, {s, visits * 4, (void **)&p.s, false}};
+    return run_over_draws(ds, n_draws, draws, visits * 4, outs, p, bl_launch_predict_scores);
 }
 
 // ---- occu_comb: the posterior predictive of its three observed sites, and its deterministic sites ----
@@ -739,10 +630,7 @@ extern "C" int bl_predict_comb(bl_dataset *ds, int n_draws, const float *draws, 
                             {scores, cells * p.Js * 4, (void **)&p.scores, false}};
     size_t largest = cells;
     for (const DrawOut &o : outs) if (o.host) largest = std::max(largest, o.bytes);
-    return run_over_draws(ds, n_draws, draws, largest, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
-        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
-        return (hipError_t)bl_launch_comb_predict(&p, grid_y, nullptr);
-    });
+    return run_over_draws(ds, n_draws, draws, largest, outs, p, bl_launch_comb_predict);
 }
 
 extern "C" int bl_deterministic_comb(bl_dataset *ds, int n_draws, const float *draws, float *psi, float *pc_prob, float *aru_prob)
@@ -757,10 +645,7 @@ extern "C" int bl_deterministic_comb(bl_dataset *ds, int n_draws, const float *d
                             {aru_prob, cells * p.aru.J * 4, (void **)&p.aru_prob, false}};
     size_t largest = cells * 4;
     for (const DrawOut &o : outs) if (o.host) largest = std::max(largest, o.bytes);
-    return run_over_draws(ds, n_draws, draws, largest, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
-        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
-        return (hipError_t)bl_launch_comb_deterministic(&p, grid_y, nullptr);
-    });
+    return run_over_draws(ds, n_draws, draws, largest, outs, p, bl_launch_comb_deterministic);
 }
 
 // ---- the posterior predictive check, fused: two discrepancies of the observed and of the replicate data per posterior draw ----
@@ -791,14 +676,7 @@ extern "C" int bl_predictive_check(bl_dataset *ds, int n_draws, const float *dra
         }
     BlPredCheckParams p{};
     p.rows = ds->d_rows; p.wraw = ds->d_wraw; p.ns = ds->n_stride; p.N = N; p.T = T; p.J = J; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = ds->D;
-    p.seed = (unsigned long long)seed;
-    p.o_u = p.o_v = p.o_e = p.o_fp = -1;
-    if (ds->model == 2) { p.fp_mode = ds->fp_mode; p.o_fp = ds->D - 1; }
-    if (ds->model == 6) {
-        const BlReModel &m = ds->re;
-        if (m.kind == 2) { p.fp_mode = m.fp_mode; p.o_fp = m.o_fp; }
-        p.o_u = m.o_u; p.o_v = m.o_v; p.o_e = m.o_e;
-    }
+    p.seed = (unsigned long long)seed; p.c = draw_coords(ds);
     p.n_blocks = (N + BL_PC_THREADS - 1) / BL_PC_THREADS;
     DevScratch scratch;
     unsigned char *d_obs = nullptr;
@@ -814,18 +692,14 @@ extern "C" int bl_predictive_check(bl_dataset *ds, int n_draws, const float *dra
                             {nullptr, by_site ? nb * 32 : 0, (void **)&p.site_part, true},
                             {nullptr, by_revisit ? nb * TJ * 8 : 0, (void **)&p.visit_exp, true},
                             {nullptr, by_revisit ? nb * TJ * 4 : 0, (void **)&p.visit_rep, true}};
-    return run_over_draws(ds, n_draws, draws, std::max<size_t>(32, nb * std::max(32, TJ * 8)), outs,
-                          [&](const float *d_draws, int n0, int n1, int grid_y) {
-                              p.draws = d_draws; p.n0 = n0; p.n1 = n1;
-                              return (hipError_t)bl_launch_predictive_check(&p, grid_y, nullptr);
-                          });
+    return run_over_draws(ds, n_draws, draws, std::max<size_t>(32, nb * std::max(32, TJ * 8)), outs, p, bl_launch_predictive_check);
 }
 
 // ---- the information criteria's two reductions of the pointwise log-likelihood, fused ----
 // (biolith/evaluation/log_likelihood.py:10-96 under lppd.py, waic.py and deviance.py.)  Kernels: predictive_density.hip.  They read what
 // bl_predictive_check reads and the caller's observation bytes, in which 255 now carries every mask.  The per-draw sums go through the
 // draws in chunks whose block partials stay within 256 MB; the per-point statistics are one launch over all the draws (its strip
-// partials do not grow with them), so no chunking can split them.
+// partials do not grow with them), so no chunking can split them: it goes out with the first chunk, when all the draws are up.
 extern "C" int bl_predictive_density(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, const uint8_t *obs, int marginal,
                                      double *per_draw, double *point_lse, double *point_var)
 {
@@ -841,154 +715,50 @@ extern "C" int bl_predictive_density(bl_dataset *ds, int n_draws, const float *d
     p.rows = ds->d_rows; p.wraw = ds->d_wraw; p.ns = ds->n_stride; p.N = N; p.T = T; p.J = J; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = ds->D;
     p.seed = (unsigned long long)seed;
     p.marginal = marginal ? 1 : 0;
-    p.n_draws = n_draws;
-    p.o_u = p.o_v = p.o_e = p.o_fp = -1;
-    if (ds->model == 2) { p.fp_mode = ds->fp_mode; p.o_fp = ds->D - 1; }
-    if (ds->model == 6) {
-        const BlReModel &m = ds->re;
-        if (m.kind == 2) { p.fp_mode = m.fp_mode; p.o_fp = m.o_fp; }
-        p.o_u = m.o_u; p.o_v = m.o_v; p.o_e = m.o_e;
-    }
+    p.n_draws = n_draws; p.c = draw_coords(ds);
+    p.n_blocks = (N + BL_PD_THREADS - 1) / BL_PD_THREADS;
     DevScratch scratch;
-    float *d_draws = nullptr;
     unsigned char *d_obs = nullptr;
-    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * ds->D * 4));
-    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * ds->D * 4, hipMemcpyHostToDevice));
     BL_HIP(scratch.alloc((void **)&d_obs, cells));
     BL_HIP(hipMemcpy(d_obs, obs, cells, hipMemcpyHostToDevice));
-    p.draws = d_draws; p.obs = d_obs;
-    if (per_draw) {
-        p.n_blocks = (N + BL_PD_THREADS - 1) / BL_PD_THREADS;
-        const size_t fit = ((size_t)256 << 20) / ((size_t)p.n_blocks * 8); // draws whose block partials fill 256 MB
-        const int chunk = (int)std::min<size_t>((size_t)n_draws, std::max<size_t>(1, fit));
-        BL_HIP(scratch.alloc((void **)&p.draw_part, (size_t)chunk * p.n_blocks * 8));
-        BL_HIP(scratch.alloc((void **)&p.per_draw, (size_t)n_draws * 8));
-        for (int n0 = 0; n0 < n_draws; n0 += chunk) {
-            p.n0 = n0; p.n1 = std::min(n0 + chunk, n_draws);
-            BL_HIP((hipError_t)bl_launch_predictive_density_draws(&p, std::min(p.n1 - p.n0, 1024), nullptr));
-        }
-        BL_HIP(hipMemcpy(per_draw, p.per_draw, (size_t)n_draws * 8, hipMemcpyDeviceToHost));
-    }
-    if (point_lse || point_var) {
+    p.obs = d_obs;
+    const bool points = point_lse || point_var;
+    if (points) {
         // strips of draws on grid.y: as many as let cells * strips fill the device, whatever the draw count
         p.strips = (int)std::min<size_t>(BL_PD_MAX_STRIPS, std::max<size_t>(1, (BL_PD_FILL + cells - 1) / cells));
         BL_HIP(scratch.alloc((void **)&p.strip_part, (size_t)p.strips * 4 * cells * 8));
         if (point_lse) BL_HIP(scratch.alloc((void **)&p.point_lse, cells * 8));
         if (point_var) BL_HIP(scratch.alloc((void **)&p.point_var, cells * 8));
-        BL_HIP((hipError_t)bl_launch_predictive_density_points(&p, nullptr));
-        if (point_lse) BL_HIP(hipMemcpy(point_lse, p.point_lse, cells * 8, hipMemcpyDeviceToHost));
-        if (point_var) BL_HIP(hipMemcpy(point_var, p.point_var, cells * 8, hipMemcpyDeviceToHost));
     }
+    const size_t part = per_draw ? (size_t)p.n_blocks * 8 : 0; // (no per-draw sums: one chunk, for the points' launch)
+    const DrawOut outs[] = {{per_draw, 8, (void **)&p.per_draw, false}, {nullptr, part, (void **)&p.draw_part, true}};
+    rc = run_over_draws(ds, n_draws, draws, part, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
+        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
+        int e = per_draw ? bl_launch_predictive_density_draws(&p, grid_y, nullptr) : 0;
+        if (!e && points && n0 == 0) {
+            e = bl_launch_predictive_density_points(&p, nullptr);
+            if (!e) e = (int)hipStreamSynchronize(nullptr); // it reads all the draws: done before run_over_draws lets go of them
+        }
+        return (hipError_t)e;
+    });
+    if (rc) return rc;
+    if (point_lse) BL_HIP(hipMemcpy(point_lse, p.point_lse, cells * 8, hipMemcpyDeviceToHost));
+    if (point_var) BL_HIP(hipMemcpy(point_var, p.point_var, cells * 8, hipMemcpyDeviceToHost));
     return BL_OK;
 }
 
 // ---- predictive counts of the count models (occu_cop, nmixture) ----
-// Poisson(lam): inversion by sequential search for lam < 10, else Hoermann's PTRS transformed rejection
-// ("The transformed rejection method for generating Poisson random variables", 1993); both exact.
-__device__ inline int bl_poisson(BlPredRng &rng, double lam)
-{
-    if (!(lam > 0.0)) return 0;
-    if (lam < 10.0) {
-        const double enlam = exp(-lam);
-        int k = 0;
-        double prod = (double)rng.uniform();
-        while (prod > enlam && k < 1000) { prod *= (double)rng.uniform(); k++; }
-        return k;
-    }
-    const double slam = sqrt(lam), loglam = log(lam);
-    const double b = 0.931 + 2.53 * slam, a = -0.059 + 0.02483 * b;
-    const double invalpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2.0);
-    for (int it = 0; it < 1000; it++) {
-        const double U = (double)rng.uniform() - 0.5, V = (double)rng.uniform();
-        const double us = 0.5 - fabs(U);
-        const double kf = floor((2.0 * a / us + b) * U + lam + 0.43);
-        if (us >= 0.07 && V <= vr) return (int)kf;
-        if (kf < 0.0 || (us < 0.013 && V > us)) continue;
-        if (log(V) + log(invalpha) - log(a / (us * us) + b) <= -lam + kf * loglam - lgamma(kf + 1.0)) return (int)kf;
-    }
-    return (int)lam;
-}
-// occu_cop (occu_cop.py:222-255, obs withheld):  z ~ Bernoulli(psi),  y_j ~ Poisson(dur_j (z lambda_j + (1 - z) f_u + f_c))
-// nmixture (nmixture.py:183-220, obs withheld):  N ~ Poisson(lambda) restricted to 0..K,  y_j ~ Binomial(N, p_j)
-__global__ void bl_predict_counts_kernel(const float *__restrict__ rows, const float *__restrict__ wraw, const float *__restrict__ dur,
-                                         int n_stride, int N, int T, int J, int Ks, int Ko, int D,
-                                         const float *__restrict__ draws, int n0, int n1, unsigned long long seed, int model,
-                                         int max_abundance, int fp_mode, int *__restrict__ latent, int *__restrict__ y,
-                                         int o_u, int o_v, int o_e, int o_fp)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    float x[BL_MAX_COVS];
-    for (int k = 0; k < Ks; k++) x[k] = rows[(size_t)k * n_stride + i];
-    for (int n = n0 + blockIdx.y; n < n1; n += gridDim.y) {
-        const float *th = draws + (size_t)n * D;
-        const float *al = th + Ks + 1;
-        float eta = th[0];
-        for (int k = 0; k < Ks; k++) eta = fmaf(x[k], th[k + 1], eta);
-        if (o_u >= 0) eta += th[o_u + i]; // random effects (offsets into a draw, -1 = absent): nmixture.py:166-172, 199-214
-        const float f = (model == 3 && fp_mode) ? __expf(th[o_fp]) : 0.0f; // (the last coordinate, or right behind the coefficients with random effects)
-        const float f_c = fp_mode == BL_FP_CONSTANT ? f : 0.0f, f_u = fp_mode == BL_FP_UNOCCUPIED ? f : 0.0f;
-        for (int t = 0; t < T; t++) {
-            BlPredRng rng(seed, ((unsigned long long)n * T + t) * N + i);
-            int zn;
-            if (model == 4) { // inversion over the renormalised truncated Poisson pmf (float64 recursion)
-                const double lam = exp((double)eta);
-                double p = exp(-lam), tot = 0.0;
-                for (int m = 0; m <= max_abundance; m++) { tot += p; p *= lam / (double)(m + 1); }
-                const double target = (double)rng.uniform() * tot;
-                p = exp(-lam);
-                double cum = 0.0;
-                zn = max_abundance;
-                for (int m = 0; m <= max_abundance; m++) {
-                    cum += p;
-                    if (target < cum) { zn = m; break; }
-                    p *= lam / (double)(m + 1);
-                }
-            } else {
-                zn = rng.uniform() < 1.0f / (1.0f + __expf(-eta)) ? 1 : 0;
-            }
-            if (latent) latent[((size_t)(n - n0) * T + t) * N + i] = zn;
-            if (!y) continue;
-            for (int j = 0; j < J; j++) {
-                const int v = t * J + j;
-                float nu = al[0];
-                for (int k = 0; k < Ko; k++) nu = fmaf(wraw[((size_t)v * Ko + k) * n_stride + i], al[k + 1], nu);
-                if (o_v >= 0) nu += th[o_v + i];
-                if (o_e >= 0) nu += th[o_e + (size_t)i * T * J + v];
-                int cnt = 0;
-                if (model == 4) {
-                    cnt = bl_binomial(rng, zn, 1.0f / (1.0f + __expf(-nu))); // Binomial(N, p), N <= 127 (pred_rng.hpp)
-                } else {
-                    const double rate = (double)dur[(size_t)v * n_stride + i] * ((zn ? (double)__expf(nu) : (double)f_u) + (double)f_c);
-                    cnt = bl_poisson(rng, rate);
-                }
-                y[(((size_t)(n - n0) * J + j) * T + t) * N + i] = cnt;
-            }
-        }
-    }
-}
-
 extern "C" int bl_predict_counts(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, int32_t *latent, int32_t *y)
 {
     int rc = per_draw_front("bl_predict_counts", ds, n_draws, draws, latent || y,
                             [](const bl_dataset *d) { return d->model == 3 || d->model == 4 || re_kind_in(d, {3, 6, 7}); },
                             "the count models occu_cop and nmixture; use bl_predict");
     if (rc || (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
-    const bool nmix_re = re_kind_in(ds, {3});   // the N-mixture model with random effects
-    const bool cop_re = re_kind_in(ds, {6, 7}); // occu_cop with random effects (and a false-positive rate: kind 7)
-    if ((ds->model == 3 || cop_re) && (rc = upload_once(&ds->d_dur, ds->h_dur))) return rc;
-    const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates, D = ds->D;
-    int *d_lat, *d_y;
-    const DrawOut outs[] = {{latent, (size_t)T * N * 4, (void **)&d_lat, false}, {y, (size_t)J * T * N * 4, (void **)&d_y, false}};
-    const size_t largest = (size_t)T * N * 4 * (y ? (size_t)J : 1); // bytes of the larger output of one draw
-    const bool re = nmix_re || cop_re;
-    return run_over_draws(ds, n_draws, draws, largest, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
-        hipLaunchKernelGGL(bl_predict_counts_kernel, dim3((N + 255) / 256, grid_y), dim3(256), 0, nullptr, ds->d_rows, ds->d_wraw, ds->d_dur,
-                           ds->n_stride, N, T, J, ds->Ks, ds->Ko, D, d_draws, n0, n1, (unsigned long long)seed,
-                           nmix_re ? 4 : (cop_re ? 3 : ds->model), ds->max_abundance, ds->fp_mode, d_lat, d_y,
-                           re ? ds->re.o_u : -1, re ? ds->re.o_v : -1, re ? ds->re.o_e : -1, cop_re && ds->fp_mode ? ds->re.o_fp : D - 1);
-        return hipGetLastError();
-    });
+    if (branch_model(ds) == 3 && (rc = upload_once(&ds->d_dur, ds->h_dur))) return rc; // occu_cop's session durations
+    BlPredictParams p = predict_params(ds, seed);
+    const size_t cells = (size_t)p.T * p.N * 4; // per draw
+    const DrawOut outs[] = {{latent, cells, (void **)&p.count_latent, false}, {y, cells * p.J, (void **)&p.count_y, false}};
+    return run_over_draws(ds, n_draws, draws, cells * (y ? (size_t)p.J : 1), outs, p, bl_launch_predict_counts);
 }
 
 extern "C" int bl_rng_streams(uint64_t seed, int chain, int nstreams, uint32_t *out)
@@ -2521,48 +2291,8 @@ extern "C" int bl_nuts_geometry(bl_dataset *ds, int *wgs_per_chain, int *threads
 }
 
 // ------------------------------------------------- deterministic sites ----
-// psi[n][t][i] = sigmoid(beta0 + x_i . beta)      (occu.py:198-207; constant over t)
-// With random effects (model 6; offsets o_u / o_v / o_e into a draw, -1 = absent, external coordinate order) the site's
-// occupancy effect joins eta, its detection effect and the replicate's effect join nu (occu.py:198-202, 221-228).
-__global__ void bl_psi_kernel(const float *__restrict__ rows, int n_stride, int N, int T, int Ks, int D,
-                              const float *__restrict__ draws, int n0, int n1, float *__restrict__ psi, int model, int o_u)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    float x[BL_MAX_COVS];
-    for (int k = 0; k < Ks; k++) x[k] = rows[(size_t)k * n_stride + i];
-    for (int n = n0 + blockIdx.y; n < n1; n += gridDim.y) {
-        const float *th = draws + (size_t)n * D;
-        float eta = th[0];
-        for (int k = 0; k < Ks; k++) eta = fmaf(x[k], th[k + 1], eta);
-        if (o_u >= 0) eta += th[o_u + i];
-        // occu: psi = sigmoid(eta) (occu.py:207); occu_rn: abundance = exp(eta) (occu_rn.py:192)
-        const float v = (model == 1 || model == 4) ? __expf(eta) : 1.0f / (1.0f + __expf(-eta));
-        for (int t = 0; t < T; t++) psi[((size_t)(n - n0) * T + t) * N + i] = v;
-    }
-}
-// prob_detection[n][j][t][i] = sigmoid(alpha0 + w_itj . alpha)   (occu.py:221-228)
-__global__ void bl_pdet_kernel(const float *__restrict__ wraw, int n_stride, int N, int T, int J, int Ks, int Ko, int D,
-                               const float *__restrict__ draws, int n0, int n1, float *__restrict__ out, int model, int o_v, int o_e)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    for (int n = n0 + blockIdx.y; n < n1; n += gridDim.y) {
-        const float *al = draws + (size_t)n * D + Ks + 1;
-        const float *th = draws + (size_t)n * D;
-        for (int t = 0; t < T; t++)
-            for (int j = 0; j < J; j++) {
-                const int v = t * J + j;
-                float nu = al[0];
-                for (int k = 0; k < Ko; k++) nu = fmaf(wraw[((size_t)v * Ko + k) * n_stride + i], al[k + 1], nu);
-                if (o_v >= 0) nu += th[o_v + i];
-                if (o_e >= 0) nu += th[o_e + (size_t)i * T * J + v];
-                // occu / occu_rn: prob_detection = sigmoid(nu); occu_cop: rate_detection = exp(nu) (occu_cop.py:236-243)
-                out[(((size_t)(n - n0) * J + j) * T + t) * N + i] = model == 3 ? __expf(nu) : 1.0f / (1.0f + __expf(-nu));
-            }
-    }
-}
-
+// psi[n][t][i] = sigmoid(beta0 + x_i . beta), prob_detection[n][j][t][i] = sigmoid(alpha0 + w_itj . alpha), with the handle's random
+// effects; the abundance models' psi and occu_cop's prob_detection are rates, exp of the predictor.  Kernels: predict.hip.
 extern "C" int bl_deterministic(bl_dataset *ds, int n_draws, const float *draws, float *psi, float *prob_detection)
 {
     if (!ds || !draws || n_draws <= 0) return bl_fail(BL_ERR_INVALID, "bl_deterministic: bad argument");
@@ -2572,38 +2302,11 @@ extern "C" int bl_deterministic(bl_dataset *ds, int n_draws, const float *draws,
         return bl_fail(BL_ERR_UNSUPPORTED, "bl_deterministic: occu_comb's sites (psi, PC / ARU detection probabilities) are formed by the caller from the draws");
     if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
     int rc = set_device(ds);
-    if (rc) return rc;
-    const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates, D = ds->D;
-    float *d_draws = nullptr, *d_out = nullptr;
-    DevScratch scratch;
-    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * D * 4));
-    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * D * 4, hipMemcpyHostToDevice));
-    // chunk the draws so the device staging buffer stays <= 256 MiB
-    const size_t per_draw = (size_t)T * N * 4 * (prob_detection ? (size_t)J : 1);
-    int chunk = (int)((256u << 20) / (per_draw ? per_draw : 1));
-    if (chunk < 1) chunk = 1;
-    if (chunk > n_draws) chunk = n_draws;
-    BL_HIP(scratch.alloc((void **)&d_out, (size_t)chunk * per_draw));
-    if (prob_detection && (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
-    const dim3 block(256);
-    for (int n0 = 0; n0 < n_draws; n0 += chunk) {
-        const int n1 = (n0 + chunk < n_draws) ? n0 + chunk : n_draws;
-        const dim3 grid((N + 255) / 256, (n1 - n0) < 1024 ? (n1 - n0) : 1024);
-        if (psi) {
-            hipLaunchKernelGGL(bl_psi_kernel, grid, block, 0, nullptr, ds->d_rows, ds->n_stride, N, T, ds->Ks, D, d_draws, n0, n1, d_out,
-                               ds->model == 6 && ds->re.kind >= 3 && ds->re.kind <= 5 ? 4 : ds->model /* N-mixture / Royle-Nichols with effects: abundance = exp(eta + u) */, ds->model == 6 ? ds->re.o_u : -1);
-            BL_HIP(hipGetLastError());
-            BL_HIP(hipMemcpy(psi + (size_t)n0 * T * N, d_out, (size_t)(n1 - n0) * T * N * 4, hipMemcpyDeviceToHost));
-        }
-        if (prob_detection) {
-            hipLaunchKernelGGL(bl_pdet_kernel, grid, block, 0, nullptr, ds->d_wraw, ds->n_stride, N, T, J, ds->Ks, ds->Ko, D, d_draws, n0, n1, d_out,
-                               ds->model == 6 && (ds->re.kind == 6 || ds->re.kind == 7) ? 3 : ds->model /* occu_cop with effects: rate_detection = exp(nu) */,
-                               ds->model == 6 ? ds->re.o_v : -1, ds->model == 6 ? ds->re.o_e : -1);
-            BL_HIP(hipGetLastError());
-            BL_HIP(hipMemcpy(prob_detection + (size_t)n0 * J * T * N, d_out, (size_t)(n1 - n0) * J * T * N * 4, hipMemcpyDeviceToHost));
-        }
-    }
-    return BL_OK;
+    if (rc || (prob_detection && (rc = upload_once(&ds->d_wraw, ds->h_wraw)))) return rc;
+    BlPredictParams p = predict_params(ds, 0);
+    const size_t cells = (size_t)p.T * p.N * 4; // per draw
+    const DrawOut outs[] = {{psi, cells, (void **)&p.psi, false}, {prob_detection, cells * p.J, (void **)&p.prob, false}};
+    return run_over_draws(ds, n_draws, draws, cells * (prob_detection ? (size_t)p.J : 1), outs, p, bl_launch_deterministic);
 }
 
 // ------------------------------------------------------- multi-GPU: the gather of the draws over RCCL ----

@@ -3,31 +3,18 @@
 //   psi = sigmoid(beta . (1, x)),  p_pc = sigmoid(alpha_PC . (1, w_pc)),  p_aru = sigmoid(alpha_ARU . (1, w_aru))
 //   z ~ Bernoulli(psi);  y_pc ~ Bernoulli(z p_pc);  y_aru ~ Bernoulli(1 - (1 - z p_aru)(1 - fc)(1 - (1 - z) fu));
 //   score ~ Normal(z ? mu1 : mu0, z ? sigma1 : sigma0)
-// The sigmoid is bl_deterministic's (1 / (1 + __expf(-x))), so the sites agree with the other models' to the same bound.
+// The sigmoid, the predictors, the false-positive composition and the normal are predict_math.hpp's: the other models' kernels call the
+// same statements, so the sites agree with theirs to the same bound.
 //
 // One thread per site, the draws on grid.y, the periods in a loop: every global access of a wavefront is contiguous, a draw's
 // coefficients are wave-uniform.  Nothing is kept per covariate (the rows are read where they are used), so no array with a run-time
-// index exists and nothing goes to scratch.  The cell's generator is bl_predict's, BlPredRng(seed, (n T + t) N + i), and it is consumed
+// index exists and nothing goes to scratch.  The cell's generator is bl_predict's (bl_cell_rng), and it is consumed
 // in one fixed order -- one uniform for z, one per point-count visit, one per ARU visit, two per score (Box-Muller, as
 // bl_predict_scores) -- whichever outputs are wanted: a NULL output never changes another one.
 #include "comb_predict.hpp"
 
 #include "posterior_math.hpp"
-#include "pred_rng.hpp"
-
-namespace {
-
-__device__ __forceinline__ float cp_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
-
-// alpha . (1, w) of visit v of a block at site i
-__device__ __forceinline__ float cp_predictor(const BlCombPredBlock &b, const float *__restrict__ al, int v, int ns, int i)
-{
-    float nu = al[0];
-    for (int k = 0; k < b.K; k++) nu = fmaf(b.w[((size_t)v * b.K + k) * ns + i], al[k + 1], nu);
-    return nu;
-}
-
-} // namespace
+#include "predict_math.hpp"
 
 __global__ void bl_comb_predict_kernel(const BlCombPredParams p)
 {
@@ -40,36 +27,32 @@ __global__ void bl_comb_predict_kernel(const BlCombPredParams p)
     for (int n = p.n0 + blockIdx.y; n < p.n1; n += gridDim.y) {
         const float *__restrict__ th = p.draws + (size_t)n * p.D;
         const float *__restrict__ apc = th + p.pc.o_al, *__restrict__ aar = th + p.aru.o_al, *__restrict__ ex = th + p.o_x;
-        float eta = th[0];
-        for (int k = 0; k < p.Ks; k++) eta = fmaf(p.rows[(size_t)k * ns + i], th[k + 1], eta);
-        const float psi = cp_sigmoid(eta);
-        const float fc = cp_sigmoid(ex[0]), fu = cp_sigmoid(ex[1]);
+        const float psi = pm_sigmoid(pm_linear(p.rows + i, ns, th, p.Ks));
+        const float fc = pm_sigmoid(ex[0]), fu = pm_sigmoid(ex[1]);
         const float mu0 = ex[2], mu1 = ex[2] + __expf(ex[3]), sg0 = __expf(ex[4]), sg1 = __expf(ex[5]);
         const size_t nb = (size_t)(n - p.n0);
         for (int t = 0; t < T; t++) {
-            BlPredRng rng(p.seed, ((unsigned long long)n * T + t) * N + i);
-            const int zn = rng.uniform() < psi ? 1 : 0;
+            BlPredRng rng = bl_cell_rng(p.seed, n, T, t, N, i);
+            const int zn = pm_draw_z(rng, psi);
             if (p.z) p.z[(nb * T + t) * N + i] = (unsigned char)zn;
             if (!need_pc) continue;
             for (int j = 0; j < Jp; j++) {
                 const float u = rng.uniform();
                 if (!p.y_pc) continue;
-                const float pd = (float)zn * cp_sigmoid(cp_predictor(p.pc, apc, t * Jp + j, ns, i));
+                const float pd = (float)zn * pm_sigmoid(pm_visit_linear(p.pc.w, ns, apc, p.pc.K, t * Jp + j, i));
                 p.y_pc[((nb * Jp + j) * T + t) * N + i] = u < pd ? 1 : 0;
             }
             if (!need_aru) continue;
             for (int j = 0; j < Ja; j++) {
                 const float u = rng.uniform();
                 if (!p.y_aru) continue;
-                const float r = (float)zn * cp_sigmoid(cp_predictor(p.aru, aar, t * Ja + j, ns, i));
-                const float pd = 1.0f - (1.0f - r) * (1.0f - fc) * (1.0f - (zn ? 0.0f : fu));
+                const float r = (float)zn * pm_sigmoid(pm_visit_linear(p.aru.w, ns, aar, p.aru.K, t * Ja + j, i));
+                const float pd = pm_false_positives(r, fc, fu, zn);
                 p.y_aru[((nb * Ja + j) * T + t) * N + i] = u < pd ? 1 : 0;
             }
             if (!need_sc) continue;
             for (int j = 0; j < Js; j++) {
-                // Box-Muller, one normal per score
-                const float u1 = fmaxf(rng.uniform(), 5.9604645e-08f), u2 = rng.uniform();
-                const float g = sqrtf(-2.0f * __logf(u1)) * __cosf(6.2831853f * u2);
+                const float g = pm_normal(rng); // one normal per score
                 p.scores[((nb * Js + j) * T + t) * N + i] = zn ? fmaf(sg1, g, mu1) : fmaf(sg0, g, mu0);
             }
         }
@@ -86,19 +69,17 @@ __global__ void bl_comb_deterministic_kernel(const BlCombPredParams p)
         const float *__restrict__ th = p.draws + (size_t)n * p.D;
         const size_t nb = (size_t)(n - p.n0);
         if (p.psi) {
-            float eta = th[0];
-            for (int k = 0; k < p.Ks; k++) eta = fmaf(p.rows[(size_t)k * ns + i], th[k + 1], eta);
-            const float psi = cp_sigmoid(eta);
+            const float psi = pm_sigmoid(pm_linear(p.rows + i, ns, th, p.Ks));
             for (int t = 0; t < T; t++) p.psi[(nb * T + t) * N + i] = psi;
         }
         if (p.pc_prob)
             for (int t = 0; t < T; t++)
                 for (int j = 0; j < Jp; j++)
-                    p.pc_prob[((nb * Jp + j) * T + t) * N + i] = cp_sigmoid(cp_predictor(p.pc, th + p.pc.o_al, t * Jp + j, ns, i));
+                    p.pc_prob[((nb * Jp + j) * T + t) * N + i] = pm_sigmoid(pm_visit_linear(p.pc.w, ns, th + p.pc.o_al, p.pc.K, t * Jp + j, i));
         if (p.aru_prob)
             for (int t = 0; t < T; t++)
                 for (int j = 0; j < Ja; j++)
-                    p.aru_prob[((nb * Ja + j) * T + t) * N + i] = cp_sigmoid(cp_predictor(p.aru, th + p.aru.o_al, t * Ja + j, ns, i));
+                    p.aru_prob[((nb * Ja + j) * T + t) * N + i] = pm_sigmoid(pm_visit_linear(p.aru.w, ns, th + p.aru.o_al, p.aru.K, t * Ja + j, i));
     }
 }
 

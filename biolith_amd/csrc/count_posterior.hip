@@ -43,11 +43,11 @@ __device__ __forceinline__ CpVisit cp_visit(const BlCountPostParams &p, const fl
     o.d = rec[ns];
     float nu = al[0];
     for (int k = 0; k < Ko; k++) nu = fmaf(rec[(size_t)(2 + k) * ns], al[k + 1], nu);
-    if (p.o_v >= 0) nu += th[p.o_v + i];
-    if (p.o_e >= 0) nu += th[p.o_e + (size_t)i * p.T * p.J + v];
+    if (p.c.o_v >= 0) nu += th[p.c.o_v + i];
+    if (p.c.o_e >= 0) nu += th[p.c.o_e + (size_t)i * p.T * p.J + v];
     nu = fminf(nu, 80.0f); // the sampler's clamp: lambda stays finite
     const float lam = bl_exp(nu), tt = lam + f1;
-    const bool with_f1 = p.fp_mode == 1 /* BL_FP_CONSTANT */;
+    const bool with_f1 = p.c.fp_mode == 1 /* BL_FP_CONSTANT */;
     const float lt = with_f1 ? bl_log(tt) : nu;
     o.a = fmaf(o.y, lt, -(o.d * tt));
     o.rho = with_f1 ? lam * bl_rcp(tt) : 1.0f;
@@ -63,18 +63,18 @@ __global__ void bl_count_posterior_kernel(const BlCountPostParams p)
     const float *__restrict__ rows = p.rows;
     const int ns = p.ns, N = p.N, T = p.T, J = p.J;
     const bool visits = p.true_mean || p.true_count;
-    const bool with_f1 = p.fp_mode == 1 /* BL_FP_CONSTANT */;
+    const bool with_f1 = p.c.fp_mode == 1 /* BL_FP_CONSTANT */;
     for (int n = p.n0 + blockIdx.y; n < p.n1; n += gridDim.y) {
         const float *__restrict__ th = p.draws + (size_t)n * p.D;
         const float *__restrict__ al = th + p.Ks + 1;
         float eta = th[0];
         for (int k = 0; k < p.Ks; k++) eta = fmaf(rows[(size_t)k * ns + i], th[k + 1], eta);
-        if (p.o_u >= 0) eta += th[p.o_u + i];
+        if (p.c.o_u >= 0) eta += th[p.c.o_u + i];
         const float ee = bl_exp(-fabsf(eta)), lop = post_log1p(ee);
         const float log_psi = fminf(eta, 0.0f) - lop, log_1mpsi = fminf(-eta, 0.0f) - lop;
         const float psi = (eta > 0.0f ? 1.0f : ee) * bl_rcp(1.0f + ee);
-        const float phi = p.fp_mode ? th[p.o_fp] : 0.0f;
-        const float f = p.fp_mode ? bl_exp(fminf(phi, 80.0f)) : 0.0f, f1 = with_f1 ? f : 0.0f;
+        const float phi = p.c.fp_mode ? th[p.c.o_fp] : 0.0f;
+        const float f = p.c.fp_mode ? bl_exp(fminf(phi, 80.0f)) : 0.0f, f1 = with_f1 ? f : 0.0f;
         for (int t = 0; t < T; t++) {
             PostSum a1, a0;
             a1.add(log_psi);
@@ -89,8 +89,8 @@ __global__ void bl_count_posterior_kernel(const BlCountPostParams p)
             const float ysum = rows[(size_t)(p.r_sum + t) * ns + i], dsum = rows[(size_t)(p.r_sum + T + t) * ns + i];
             const float cc = p.ccell[(size_t)t * ns + i];
             a1.add(cc);
-            const bool dead0 = !p.fp_mode && ysum > 0.0f; // Poisson(0) met a positive count (a Kahan step on -inf would leave inf - inf)
-            if (p.fp_mode) a0.add(fmaf(ysum, phi, -(dsum * f)));
+            const bool dead0 = !p.c.fp_mode && ysum > 0.0f; // Poisson(0) met a positive count (a Kahan step on -inf would leave inf - inf)
+            if (p.c.fp_mode) a0.add(fmaf(ysum, phi, -(dsum * f)));
             a0.add(cc);
             const float A = a1.s, B = dead0 ? -INFINITY : a0.s;
             const float dd = A - B, e = bl_exp(-fabsf(dd));
@@ -101,7 +101,7 @@ __global__ void bl_count_posterior_kernel(const BlCountPostParams p)
             if (p.log_lik) p.log_lik[o] = l;
             if (p.z_prob) p.z_prob[o] = q;
             if (!p.z && !visits) continue;
-            BlPredRng rng(p.seed, ((unsigned long long)n * T + t) * N + i);
+            BlPredRng rng = bl_cell_rng(p.seed, n, T, t, N, i);
             const bool zn = rng.uniform() < q;
             if (p.z) p.z[o] = zn ? 1 : 0;
             if (!visits) continue;

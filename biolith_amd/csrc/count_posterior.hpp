@@ -7,13 +7,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "draw_coords.hpp"
+
 struct BlCountPostParams {
     const float *rows;        // [n_rows][ns], site-fastest; rows 0 .. Ks - 1 = the site covariates, visit v at rows r0 + v * vw .. + vw - 1
     const float *ccell;       // [T][ns]: sum over the cell's unmasked visits of y log d - lgamma(y + 1)
     int ns, N, T, J, Ks, Ko, D;
     int r0, vw, r_sum;        // Ysum of period t at row r_sum + t, Dsum at row r_sum + T + t
-    int fp_mode;              // 0, BL_FP_CONSTANT (1), BL_FP_UNOCCUPIED (2)
-    int o_fp, o_u, o_v, o_e;  // offsets into a draw: phi = log rate, site_re_occ [N], site_re_det [N], obs_re [N][T][J]; -1 = absent
+    BlDrawCoords c;           // the false-positive rate (phi = log rate) and the random effects in a draw
     const float *draws;       // [n_draws][D], device: [beta | alpha | (phi) | (log sds) | (effects)]
     int n0, n1;               // the draws of this launch; outputs are indexed from n0
     unsigned long long seed;

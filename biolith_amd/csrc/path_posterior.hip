@@ -95,7 +95,7 @@ __global__ void bl_path_posterior_kernel(const BlPathPostParams p)
         post_sig(d, rho, nrho);
         bool zb = false;
         if (p.z) {
-            BlPredRng rng(p.seed, ((unsigned long long)n * T + (T - 1)) * N + i);
+            BlPredRng rng = bl_cell_rng(p.seed, n, T, T - 1, N, i);
             zb = rng.uniform() < rho;
             p.z[o_cell + (size_t)(T - 1) * N] = zb ? 1 : 0;
         }
@@ -110,7 +110,7 @@ __global__ void bl_path_posterior_kernel(const BlPathPostParams p)
             if (p.col_prob) p.col_prob[o_pair + (size_t)t * N] = xi01;
             if (p.ext_prob) p.ext_prob[o_pair + (size_t)t * N] = xi10;
             if (p.z) {
-                BlPredRng rng(p.seed, ((unsigned long long)n * T + t) * N + i);
+                BlPredRng rng = bl_cell_rng(p.seed, n, T, t, N, i);
                 zb = rng.uniform() < (zb ? b1 : b0);
                 p.z[o_cell + (size_t)t * N] = zb ? 1 : 0;
             }

@@ -1,6 +1,7 @@
-// posterior_math.hpp -- the arithmetic and the launch geometry the three post-fit kernels share (site_posterior.hip,
-// abundance_posterior.hip, path_posterior.hip).  Every expression is written once, here: -ffp-contract=on fuses per source expression,
-// so a helper restated in another file is a chance of last-bit differences between kernels that state the same quantity.
+// posterior_math.hpp -- the arithmetic and the launch geometry the conditional-posterior kernels share (site_, abundance_, path_, score_
+// and count_posterior.hip; comb_predict.hip takes the geometry).  Every expression is written once, here: -ffp-contract=on fuses per
+// source expression, so a helper restated in another file is a chance of last-bit differences between kernels that state the same
+// quantity.  The posterior predictive's arithmetic is stated the same way in predict_math.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -26,6 +26,11 @@ struct BlPredRng {
         return (float)(r >> 8) * 5.9604644775390625e-08f;
     }
 };
+// the generator of cell (draw n, period t of T, site i of N), n the absolute draw index
+__device__ inline BlPredRng bl_cell_rng(unsigned long long seed, int n, int T, int t, int N, int i)
+{
+    return BlPredRng(seed, ((unsigned long long)n * T + t) * N + i);
+}
 // Binomial(n, p) as n Bernoulli trials, one uniform each: exact, and the number of uniforms is n whatever p is
 // (nmixture's predictive counts, n <= 127; occu_cop's true detections among a visit's count)
 __device__ inline int bl_binomial(BlPredRng &rng, int n, float p)

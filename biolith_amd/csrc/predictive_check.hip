@@ -1,8 +1,8 @@
 // predictive_check.hip -- the kernels of bl_predictive_check: the posterior predictive check's two discrepancies per posterior draw
 // (biolith/evaluation/posterior_predictive_check.py:17-160), without the replicate-level arrays it is stated on.
-//   y_rep = bl_predict's replicate, regenerated: the cell's generator BlPredRng(seed, (n T + t) N + i), z first, one uniform per visit,
-//           the arithmetic of bl_predict_kernel restated here (occu, false positives, random effects) -- bit for bit its y
-//   E     = (double)psi (double)p, psi and p the float32 values of bl_deterministic (same fmaf chain, same 1 / (1 + __expf(-x))):
+//   y_rep = bl_predict's replicate, regenerated: the cell's generator (bl_cell_rng), z first, one uniform per visit, through the
+//           statements bl_predict_kernel calls (predict_math.hpp: occu, false positives, random effects) -- bit for bit its y
+//   E     = (double)psi (double)p, psi and p the float32 values of bl_deterministic (the same calls into predict_math.hpp):
 //           the product of two float32 is exact in float64, so E is what the host check forms from predict()'s arrays
 //   seen  = the caller's observation is not 255; nothing else masks
 //   ft(o, e) = (sqrt o - sqrt e)^2,  chi(o, e) = (o - e)^2 / (e + 1e-10),  float64
@@ -15,7 +15,7 @@
 // the revisit statistics.  No floating-point atomic anywhere: two runs give the same bits.  Nothing of size (n, J, T, N) exists.
 #include "predictive_check.hpp"
 
-#include "pred_rng.hpp"
+#include "predict_math.hpp"
 
 namespace {
 
@@ -61,31 +61,24 @@ __global__ __launch_bounds__(BL_PC_THREADS) void bl_predictive_check_kernel(cons
         const size_t part = (size_t)(n - p.n0) * p.n_blocks + blockIdx.x;
         float psi = 0.0f, f_c = 0.0f, f_u = 0.0f;
         if (live) {
-            float eta = th[0];
-            for (int k = 0; k < Ks; k++) eta = fmaf(p.rows[(size_t)k * ns + i], th[k + 1], eta);
-            if (p.o_u >= 0) eta += th[p.o_u + i];
-            psi = 1.0f / (1.0f + __expf(-eta));
-            const float fpr = p.fp_mode ? 1.0f / (1.0f + __expf(-th[p.o_fp])) : 0.0f;
-            f_c = p.fp_mode == 1 ? fpr : 0.0f;
-            f_u = p.fp_mode == 2 ? fpr : 0.0f;
+            psi = pm_sigmoid(pm_site_eta(p.rows + i, ns, th, Ks, p.c, i));
+            const float fpr = p.c.fp_mode ? pm_sigmoid(th[p.c.o_fp]) : 0.0f;
+            f_c = p.c.fp_mode == 1 ? fpr : 0.0f;
+            f_u = p.c.fp_mode == 2 ? fpr : 0.0f;
         }
         int s_obs = 0, s_rep = 0; // the site's seen visits: observed and replicate detections, expectation
         double s_exp = 0.0;
         for (int t = 0; t < T; t++) {
-            BlPredRng rng(p.seed, ((unsigned long long)n * T + t) * N + (live ? i : 0));
-            const int zn = live && rng.uniform() < psi ? 1 : 0;
+            BlPredRng rng = bl_cell_rng(p.seed, n, T, t, N, live ? i : 0);
+            const int zn = live ? pm_draw_z(rng, psi) : 0;
             for (int j = 0; j < J; j++) {
                 const int v = t * J + j;
                 int c = 0;
                 double e = 0.0;
                 if (live) {
-                    float nu = al[0];
-                    for (int k = 0; k < Ko; k++) nu = fmaf(p.wraw[((size_t)v * Ko + k) * ns + i], al[k + 1], nu);
-                    if (p.o_v >= 0) nu += th[p.o_v + i];
-                    if (p.o_e >= 0) nu += th[p.o_e + (size_t)i * T * J + v];
-                    const float r = 1.0f / (1.0f + __expf(-nu));
+                    const float r = pm_sigmoid(pm_visit_nu(p.wraw, ns, th, al, Ko, p.c, T, J, v, i));
                     float pd = (float)zn * r;
-                    if (p.fp_mode) pd = 1.0f - (1.0f - pd) * (1.0f - f_c) * (1.0f - (zn ? 0.0f : f_u));
+                    if (p.c.fp_mode) pd = pm_false_positives(pd, f_c, f_u, zn);
                     const float u = rng.uniform();
                     const int o = p.obs[((size_t)j * T + t) * N + i];
                     if (o != 255) {

@@ -7,15 +7,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "draw_coords.hpp"
+
 constexpr int BL_PC_THREADS = 256; // sites per block: four wave64
 
 struct BlPredCheckParams {
     const float *rows;         // rows 0 .. Ks - 1 = the site covariates, [.][ns], NaN -> 0
     const float *wraw;         // [T J][Ko][ns], site-fastest, NaN -> 0
     int ns, N, T, J, Ks, Ko, D;
-    int fp_mode;               // 0, BL_FP_CONSTANT (1), BL_FP_UNOCCUPIED (2); phi = logit(rate) at o_fp
-    int o_fp;
-    int o_u, o_v, o_e;         // random effects in a draw (external order: [N], [N], [N][T][J]); -1 = absent
+    BlDrawCoords c;            // the false-positive rate (phi = logit(rate)) and the random effects in a draw
     const float *draws;        // [n_draws][D], device
     int n0, n1;                // the draws of this launch; partials and results are indexed from n0
     unsigned long long seed;

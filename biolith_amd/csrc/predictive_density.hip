@@ -1,8 +1,8 @@
 // predictive_density.hip -- the kernels of bl_predictive_density: the pointwise log-likelihood of the observations under every posterior
 // draw, reduced two ways without ever being stored (biolith/evaluation/log_likelihood.py:10-96 and what lppd.py, waic.py and deviance.py
 // reduce it to).  Per draw n, visit (t, j) and site i, in float64:
-//   psi, r = the float32 values of bl_deterministic (same fmaf chain, same 1 / (1 + __expf(-x)), the random effects added as there)
-//   conditional:  z = bl_predict's draw: the first uniform of BlPredRng(seed, (n T + t) N + i) < psi
+//   psi, r = the float32 values of bl_deterministic (the same calls into predict_math.hpp)
+//   conditional:  z = bl_predict's draw: the first uniform of the cell's generator (bl_cell_rng) < psi
 //                 prob = z r, or with a false-positive rate f (constant: f_c = f; unoccupied: f_u = f)
 //                 prob = 1 - (1 - z r)(1 - f_c)(1 - (1 - z) f_u), each product rounded once (the expression as NumPy evaluates it)
 //                 f = (float)(1 / (1 + exp(-(double)phi))): the float32 site value that the layout's sigmoid transform gives the
@@ -26,7 +26,7 @@
 
 #include <cfloat>
 
-#include "pred_rng.hpp"
+#include "predict_math.hpp"
 
 namespace {
 
@@ -49,32 +49,25 @@ __device__ __forceinline__ PdDraw pd_draw(const BlPredDensityParams &p, int n)
     d.th = p.draws + (size_t)n * p.D;
     d.al = d.th + p.Ks + 1;
     d.f_c = d.f_u = 0.0f;
-    if (p.fp_mode && !p.marginal) {
-        const double e = exp(-(double)d.th[p.o_fp]);
+    if (p.c.fp_mode && !p.marginal) {
+        const double e = exp(-(double)d.th[p.c.o_fp]); // (float64 on purpose: see the header)
         const float f = (float)(1.0 / (1.0 + e));
-        if (p.fp_mode == 1) d.f_c = f; else d.f_u = f;
+        if (p.c.fp_mode == 1) d.f_c = f; else d.f_u = f;
     }
     return d;
 }
 __device__ __forceinline__ float pd_psi(const BlPredDensityParams &p, const PdDraw &d, int i)
 {
-    float eta = d.th[0];
-    for (int k = 0; k < p.Ks; k++) eta = fmaf(p.rows[(size_t)k * p.ns + i], d.th[k + 1], eta);
-    if (p.o_u >= 0) eta += d.th[p.o_u + i];
-    return 1.0f / (1.0f + __expf(-eta));
+    return pm_sigmoid(pm_site_eta(p.rows + i, p.ns, d.th, p.Ks, p.c, i));
 }
 __device__ __forceinline__ float pd_r(const BlPredDensityParams &p, const PdDraw &d, int i, int v)
 {
-    float nu = d.al[0];
-    for (int k = 0; k < p.Ko; k++) nu = fmaf(p.wraw[((size_t)v * p.Ko + k) * p.ns + i], d.al[k + 1], nu);
-    if (p.o_v >= 0) nu += d.th[p.o_v + i];
-    if (p.o_e >= 0) nu += d.th[p.o_e + (size_t)i * p.T * p.J + v];
-    return 1.0f / (1.0f + __expf(-nu));
+    return pm_sigmoid(pm_visit_nu(p.wraw, p.ns, d.th, d.al, p.Ko, p.c, p.T, p.J, v, i));
 }
 __device__ __forceinline__ int pd_z(const BlPredDensityParams &p, int n, int t, int i, float psi)
 {
-    BlPredRng rng(p.seed, ((unsigned long long)n * p.T + t) * p.N + i);
-    return rng.uniform() < psi ? 1 : 0;
+    BlPredRng rng = bl_cell_rng(p.seed, n, p.T, t, p.N, i);
+    return pm_draw_z(rng, psi);
 }
 __device__ __forceinline__ double pd_loglik(const BlPredDensityParams &p, const PdDraw &d, int y, float psi, float r, int zn)
 {
@@ -84,7 +77,7 @@ __device__ __forceinline__ double pd_loglik(const BlPredDensityParams &p, const 
         return log(fmin(fmax(a, 1e-10), 1.0 - 1e-10));
     }
     double prob = zn ? (double)r : 0.0;
-    if (p.fp_mode) {
+    if (p.c.fp_mode) {
         const double a = 1.0 - prob, b = 1.0 - (double)d.f_c, c = 1.0 - (zn ? 0.0 : (double)d.f_u);
         const double ab = a * b; // (a statement each: nothing contracts into an fma, the products round as on the host)
         const double abc = ab * c;
@@ -137,7 +130,7 @@ __global__ void bl_predictive_density_draws_finish_kernel(const BlPredDensityPar
     if (m >= p.n1 - p.n0) return;
     double a = 0.0;
     for (int b = 0; b < p.n_blocks; b++) a += p.draw_part[(size_t)m * p.n_blocks + b];
-    p.per_draw[p.n0 + m] = a;
+    p.per_draw[m] = a;
 }
 
 __global__ __launch_bounds__(BL_PD_THREADS) void bl_predictive_density_points_kernel(const BlPredDensityParams p)

@@ -8,6 +8,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "draw_coords.hpp"
+
 constexpr int BL_PD_THREADS = 256;    // threads per block of both main kernels: four wave64
 constexpr int BL_PD_MAX_STRIPS = 64;  // the cap of the point kernel's strips of draws (grid.y); it does not depend on the draw count
 constexpr int BL_PD_FILL = 256 * 2048; // threads that fill the device: the strip count is chosen so that cells * strips reaches it
@@ -16,19 +18,17 @@ struct BlPredDensityParams {
     const float *rows;         // rows 0 .. Ks - 1 = the site covariates, [.][ns], NaN -> 0
     const float *wraw;         // [T J][Ko][ns], site-fastest, NaN -> 0
     int ns, N, T, J, Ks, Ko, D;
-    int fp_mode;               // 0, BL_FP_CONSTANT (1), BL_FP_UNOCCUPIED (2); phi = logit(rate) at o_fp
-    int o_fp;
-    int o_u, o_v, o_e;         // random effects in a draw (external order: [N], [N], [N][T][J]); -1 = absent
+    BlDrawCoords c;            // the false-positive rate (phi = logit(rate)) and the random effects in a draw
     const float *draws;        // [n_draws][D], device: all of them
     int n_draws;
-    int n0, n1;                // the draws of one launch of the per-draw kernel; its partials are indexed from n0
+    int n0, n1;                // the draws of one launch of the per-draw kernel; its partials and results are indexed from n0
     unsigned long long seed;
     const unsigned char *obs;  // [J][T][N], device: 0, 1, 255 = not a point
     int marginal;              // 0: the conditional form at predict()'s z; 1: the marginal form psi * r (no generator)
     // per draw: the sum of ll over the points
     int n_blocks;              // site blocks = gridDim.x of the per-draw kernel
     double *draw_part;         // [n1 - n0][n_blocks], device workspace
-    double *per_draw;          // [n_draws], device
+    double *per_draw;          // [n1 - n0], device
     // per point: log mean exp and variance of ll over the draws
     int strips;                // gridDim.y of the point kernel: strip r walks the draws [bl_pd_strip_begin(r), bl_pd_strip_begin(r + 1))
     double *strip_part;        // [strips][4][J T N], device workspace: running maximum, scaled sum of exponentials, mean, M2

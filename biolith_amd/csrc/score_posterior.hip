@@ -96,7 +96,7 @@ __global__ void bl_score_posterior_kernel(const BlScorePostParams p)
             if (p.log_lik) p.log_lik[o] = l;
             if (p.z_prob) p.z_prob[o] = q;
             if (!p.z && !visits) continue;
-            BlPredRng rng(p.seed, ((unsigned long long)n * T + t) * N + i);
+            BlPredRng rng = bl_cell_rng(p.seed, n, T, t, N, i);
             const bool zn = rng.uniform() < q;
             if (p.z) p.z[o] = zn ? 1 : 0;
             if (!visits) continue;

@@ -41,8 +41,8 @@ __global__ void bl_site_posterior_kernel(const BlSitePostParams p)
         const float *__restrict__ th = p.draws + (size_t)n * p.D;
         float eta = th[0];
         for (int k = 0; k < p.Ks; k++) eta = fmaf(rows[(size_t)k * ns + i], th[k + 1], eta);
-        if (p.o_u >= 0) eta += th[p.o_u + i];
-        const float vi = p.o_v >= 0 ? th[p.o_v + i] : 0.0f;
+        if (p.c.o_u >= 0) eta += th[p.c.o_u + i];
+        const float vi = p.c.o_v >= 0 ? th[p.c.o_v + i] : 0.0f;
         const float ee = bl_exp(-fabsf(eta)), lop = post_log1p(ee);
         const float log_psi = fminf(eta, 0.0f) - lop, log_1mpsi = fminf(-eta, 0.0f) - lop;
         const float psi = (eta > 0.0f ? 1.0f : ee) * bl_rcp(1.0f + ee);
@@ -58,10 +58,10 @@ __global__ void bl_site_posterior_kernel(const BlSitePostParams p)
             mu0 = th[p.o_x + 2]; mu1 = mu0 + bl_exp(th[p.o_x + 3]);
             c0 = th[p.o_x + 4] + SP_HL2PI; c1 = th[p.o_x + 5] + SP_HL2PI;              // log sigma + log(2 pi) / 2
             is0 = bl_exp(-2.0f * th[p.o_x + 4]); is1 = bl_exp(-2.0f * th[p.o_x + 5]);  // 1 / sigma^2
-        } else if (p.fp_mode) {
+        } else if (p.c.fp_mode) {
             float f, g;
-            sp_rate(th[p.o_fp], f, g, z0_det, z0_non);
-            if (p.fp_mode == 1) { f1 = f; l1f1 = z0_non; }
+            sp_rate(th[p.c.o_fp], f, g, z0_det, z0_non);
+            if (p.c.fp_mode == 1) { f1 = f; l1f1 = z0_non; }
         }
         for (int t = 0; t < T; t++) {
             PostSum a1;
@@ -77,7 +77,7 @@ __global__ void bl_site_posterior_kernel(const BlSitePostParams p)
                 for (int k = 1; k <= p.a.K; k++) u = fmaf(rows[r + (size_t)k * ns], al[k], u);
                 if constexpr (!COMB) {
                     float re = vi;
-                    if (p.o_e >= 0) re += th[(size_t)p.o_e + (size_t)i * T * p.a.J + v];
+                    if (p.c.o_e >= 0) re += th[(size_t)p.c.o_e + (size_t)i * T * p.a.J + v];
                     u = fmaf(c, re, u);
                 }
                 const float e = bl_exp(-fabsf(u)), lsu = fminf(u, 0.0f) - post_log1p(e); // log sigma(u)
@@ -134,7 +134,7 @@ __global__ void bl_site_posterior_kernel(const BlSitePostParams p)
             if (p.log_lik) p.log_lik[o] = l;
             if (p.z_prob) p.z_prob[o] = q;
             if (p.z) {
-                BlPredRng rng(p.seed, ((unsigned long long)n * T + t) * N + i);
+                BlPredRng rng = bl_cell_rng(p.seed, n, T, t, N, i);
                 p.z[o] = rng.uniform() < q ? 1 : 0;
             }
         }

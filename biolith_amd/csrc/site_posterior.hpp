@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "draw_coords.hpp"
+
 // one block of visits: first row, replicates per period, covariates, rows per visit, where its K + 1 coefficients start in a draw
 struct BlSitePostBlock {
     int r0, J, K, vw, o_al;
@@ -17,9 +19,7 @@ struct BlSitePostParams {
     BlSitePostBlock b;        // occu_comb: the ARU visits (J = 0 otherwise)
     int comb;                 // 1 = occu_comb: block b, six rows per period from r_per, the six trailing coordinates from o_x
     int r_per, o_x;
-    int fp_mode;              // occu: 0, BL_FP_CONSTANT (1), BL_FP_UNOCCUPIED (2); phi = logit(rate) at o_fp
-    int o_fp;
-    int o_u, o_v, o_e;        // random effects in a draw (external order: [N], [N], [N][T][J]); -1 = absent
+    BlDrawCoords c;           // occu: the false-positive rate (phi = logit(rate)) and the random effects in a draw
     const float *draws;       // [n_draws][D], device
     int n0, n1;               // the draws of this launch; outputs are indexed from n0
     unsigned long long seed;
