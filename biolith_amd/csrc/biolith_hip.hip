@@ -28,6 +28,7 @@
 #include "comb_predict.hpp"
 #include "predictive_check.hpp"
 #include "predictive_density.hpp"
+#include "psis_loo.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -744,6 +745,52 @@ extern "C" int bl_predictive_density(bl_dataset *ds, int n_draws, const float *d
     if (rc) return rc;
     if (point_lse) BL_HIP(hipMemcpy(point_lse, p.point_lse, cells * 8, hipMemcpyDeviceToHost));
     if (point_var) BL_HIP(hipMemcpy(point_var, p.point_var, cells * 8, hipMemcpyDeviceToHost));
+    return BL_OK;
+}
+
+// ---- PSIS-LOO of a (draws, cells) log-likelihood matrix ----
+// (No counterpart in the reference.)  Kernels: psis_loo.hip.  The entry knows no model and takes no handle: the matrix is what any
+// conditional posterior returned.  Cells go up in ranges -- a strided copy each -- whose workspace (the range as uploaded, its transpose
+// and three doubles per cell) stays within 256 MB; a cell's outputs do not depend on the range it travels in.
+extern "C" int bl_psis_loo(int device, int n_draws, int64_t cells, const float *log_lik, int64_t cells_per_launch, double *elpd,
+                           double *pareto_k, double *lppd)
+{
+    if (!log_lik) return bl_fail(BL_ERR_INVALID, "bl_psis_loo: log_lik is NULL");
+    if (!elpd && !pareto_k && !lppd) return bl_fail(BL_ERR_INVALID, "bl_psis_loo: every output is NULL");
+    if (n_draws < 2) return bl_fail(BL_ERR_INVALID, "bl_psis_loo: n_draws=%d (at least 2 draws)", n_draws);
+    if (cells < 0 || cells_per_launch < 0 || device < 0)
+        return bl_fail(BL_ERR_INVALID, "bl_psis_loo: cells=%lld, cells_per_launch=%lld, device=%d", (long long)cells,
+                       (long long)cells_per_launch, device);
+    if (n_draws > BL_PSIS_MAX_DRAWS)
+        return bl_fail(BL_ERR_UNSUPPORTED, "bl_psis_loo: n_draws=%d above BL_PSIS_MAX_DRAWS=%d", n_draws, BL_PSIS_MAX_DRAWS);
+    if (cells == 0) return BL_OK;
+    BlPsisParams p{};
+    p.n = n_draws;
+    p.tail = (int)std::ceil(std::min(n_draws / 5.0, 3.0 * std::sqrt((double)n_draws)));
+    if (p.tail > BL_PSIS_TAIL_MAX) return bl_fail(BL_ERR_UNSUPPORTED, "bl_psis_loo: tail of %d draws above %d", p.tail, BL_PSIS_TAIL_MAX);
+    const size_t per_cell = (size_t)n_draws * 8 + 24;
+    int64_t chunk = std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / per_cell));
+    if (cells_per_launch > 0) chunk = std::min(chunk, cells_per_launch);
+    chunk = std::min(chunk, cells);
+    BL_HIP(hipSetDevice(device));
+    DevScratch scratch;
+    float *d_in = nullptr;
+    BL_HIP(scratch.alloc((void **)&d_in, (size_t)chunk * n_draws * 4));
+    BL_HIP(scratch.alloc((void **)&p.cols, (size_t)chunk * n_draws * 4));
+    BL_HIP(scratch.alloc((void **)&p.out, (size_t)chunk * 3 * 8));
+    p.in = d_in;
+    double *const outs[3] = {elpd, pareto_k, lppd};
+    for (int64_t c0 = 0; c0 < cells; c0 += chunk) {
+        const int64_t cc = std::min(chunk, cells - c0);
+        p.cells = (int)cc;
+        if (cc == cells) // (one range: the matrix as it lies)
+            BL_HIP(hipMemcpy(d_in, log_lik, (size_t)cells * n_draws * 4, hipMemcpyHostToDevice));
+        else
+            BL_HIP(hipMemcpy2D(d_in, (size_t)cc * 4, log_lik + c0, (size_t)cells * 4, (size_t)cc * 4, (size_t)n_draws, hipMemcpyHostToDevice));
+        BL_HIP((hipError_t)bl_launch_psis_loo(&p, nullptr));
+        for (int o = 0; o < 3; o++)
+            if (outs[o]) BL_HIP(hipMemcpy(outs[o] + c0, p.out + (size_t)o * cc, (size_t)cc * 8, hipMemcpyDeviceToHost));
+    }
     return BL_OK;
 }
 

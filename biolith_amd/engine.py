@@ -633,3 +633,18 @@ def adaptation_schedule(num_warmup: int):
     e = (C.c_int32 * 40)()
     n = _ffi.load().bl_adaptation_schedule(int(num_warmup), s, e, 40)
     return [(s[i], e[i]) for i in range(n)]
+
+
+def psis_loo(log_lik, device: int = 0, cells_per_launch: int = 0):
+    """PSIS-LOO of every cell of a log-likelihood array ``(n, ...)``: ``(elpd, pareto_k, lppd)``, float64 of shape ``log_lik.shape[1:]``
+    (include/biolith_hip.h: bl_psis_loo, where the definition is).  ``log_lik`` is what any conditional posterior returns; it is passed
+    as float32.  A cell whose column holds a non-finite value is NaN in all three.  ``cells_per_launch`` (0: chosen by the library) only
+    sets how many cells travel to the device together; it changes no bit of the result."""
+    ll = np.asarray(log_lik, dtype=np.float32)
+    if ll.ndim < 1:
+        raise ValueError("psis_loo(): log_lik must have the draws on its first axis")
+    shape = ll.shape[1:]
+    ll = np.ascontiguousarray(ll.reshape(ll.shape[0], -1))
+    outs = [np.empty(ll.shape[1], dtype=np.float64) for _ in range(3)]
+    _ffi.check(_ffi.load().bl_psis_loo(int(device), int(ll.shape[0]), int(ll.shape[1]), _fp(ll), int(cells_per_launch), *map(_dp, outs)))
+    return tuple(o.reshape(shape) for o in outs)

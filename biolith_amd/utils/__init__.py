@@ -5,11 +5,12 @@ from .grid_search import GridSearchResult, grid_search_priors
 from .information_criteria import information_criteria
 from .init import init_to_feasible, init_to_mean, init_to_median, init_to_sample, init_to_uniform, init_to_value
 from .latent import conditional_occupancy
+from .loo import compare_marginal, loo_marginal
 from .predict import predict
 from .predict_comb import predict_comb
 from .predictive_check import predictive_check
 from .scores import conditional_scores
 from .counts import conditional_counts
 
-__all__ = ["fit", "FitResult", "predict", "predict_comb", "predictive_check", "information_criteria", "conditional_occupancy", "conditional_abundance", "conditional_dynamics", "conditional_scores", "conditional_counts", "grid_search_priors", "GridSearchResult", "init_to_uniform", "init_to_feasible", "init_to_value",
+__all__ = ["fit", "FitResult", "predict", "predict_comb", "predictive_check", "information_criteria", "conditional_occupancy", "conditional_abundance", "conditional_dynamics", "conditional_scores", "conditional_counts", "loo_marginal", "compare_marginal", "grid_search_priors", "GridSearchResult", "init_to_uniform", "init_to_feasible", "init_to_value",
            "init_to_mean", "init_to_median", "init_to_sample"]

@@ -433,6 +433,30 @@ int bl_predictive_density(bl_dataset *ds, int n_draws, const float *draws, uint6
                           double *per_draw, double *point_lse, double *point_var);
 
 /*
+ * PSIS-LOO -- BUILDER-DEFINED, NO REFERENCE COUNTERPART: Pareto-smoothed importance-sampling leave-one-out (Vehtari, Simpson, Gelman, Yao
+ * and Gabry; the generalised-Pareto fit is Zhang and Stephens' profile posterior mean) of every cell of a log-likelihood matrix
+ * log_lik [n_draws][cells], float32 on the host -- the log_lik any conditional posterior below returns, its trailing axes folded into the
+ * cells.  The entry knows no model and takes no handle.  Per cell, in float64, with ll the cell's column:
+ *   lr = -ll - max(-ll);  M = ceil(min(n / 5, 3 sqrt(n)));  cut = max((M+1)-th largest lr, log(DBL_MIN))  (n < 5: the smallest lr)
+ *   the tail is {lr > cut}, M' draws.  M' <= 4: k = inf, lr stays.  Otherwise, with x_i = exp(lr_(i)) - exp(cut) ascending,
+ *   m = 30 + floor(sqrt(M')), b_j = (1 - sqrt(m / (j - 0.5))) / (3 x[floor(M'/4 + 0.5) - 1]) + 1 / x_max  (j = 1 .. m),
+ *   kk_j = mean_i log1p(-b_j x_i), L_j = M' (log(-b_j / kk_j) - kk_j - 1), w_j = 1 / sum_l exp(L_l - L_j), w_j < 10 DBL_EPSILON dropped
+ *   and the rest renormalised, b = sum_j w_j b_j, kk = mean_i log1p(-b x_i), sigma = -kk / b, k = (M' kk + 5) / (M' + 10); if k is
+ *   finite the i-th smallest tail draw gets lr = min(log(sigma q_i + exp(cut)), 0), q_i = expm1(-k log1p(-p_i)) / k, p_i = (i + 0.5) / M'
+ *   (q_i = -log1p(-p_i) if |k| < 1e-15)
+ *   lw = lr - logsumexp(lr):   elpd = logsumexp(lw + ll),   pareto_k = k,   lppd = logsumexp(ll) - log n
+ * elpd, pareto_k and lppd are [cells] float64 on the host, NULL = skip (all three NULL: BL_ERR_INVALID).  A column that holds a
+ * non-finite value gets NaN in all three and changes no other cell.  A cell's outputs are a function of its column alone: every sum runs
+ * in a fixed order (no floating-point atomics), and neither the neighbouring cells nor cells_per_launch change a bit.  The cells go to the
+ * device in ranges of cells_per_launch (0: as many as keep the device workspace -- the range, its transpose and the outputs -- within
+ * 256 MB; a larger request is cut to that).  n_draws < 2, cells < 0, cells_per_launch < 0 or a NULL matrix: BL_ERR_INVALID; n_draws above
+ * BL_PSIS_MAX_DRAWS: BL_ERR_UNSUPPORTED, the message names the cap; both before anything is launched.  cells == 0 succeeds.
+ */
+#define BL_PSIS_MAX_DRAWS 8192
+int bl_psis_loo(int device, int n_draws, int64_t cells, const float *log_lik, int64_t cells_per_launch, double *elpd, double *pareto_k,
+                double *lppd);
+
+/*
  * Conditional occupancy -- BUILDER-DEFINED, NO REFERENCE COUNTERPART (biolith/utils/predict.py withholds the observations, so its z
  * is drawn from the prior).  Per posterior draw and (period, site), with the site-period's unmasked observations `obs`:
  *   A = log psi + log p(obs | z = 1),   B = log(1 - psi) + log p(obs | z = 0)         (the terms, clamps and masks of bl_logp_grad)
