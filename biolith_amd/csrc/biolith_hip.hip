@@ -2077,6 +2077,7 @@ extern "C" int bl_nuts_launch(bl_dataset *ds, const bl_nuts_config *cfg, void *s
     ds->d_rng = (uint32_t *)(base + o_rng); ds->d_init = (float *)(base + o_init); ds->d_dbg = (long long *)(base + o_dbg); ds->d_loc = (int *)(base + o_loc);
     int pitch = nvp; // granules between workgroup records
     { const char *e = bl_env(BL_ENV_PITCH); if (e && atoi(e) >= nvp && atoi(e) <= 4096) pitch = atoi(e); }
+    pitch += pitch & 1; // (even: the paired records' 16-byte loads stay aligned -- nuts_kernel.hpp BL_POLL_PAIRS)
     const size_t xb = align256((size_t)C * BL_XCHG_SLOTS * k * pitch * 8);
     if (xb > ds->xchg_bytes) {
         if (ds->d_xchg) hipFree(ds->d_xchg);

@@ -26,6 +26,10 @@
 //         the XCD's L2, sc1 polls bypass L1 and hit that L2: several times shorter hop;
 //     every workgroup sums the k records in the same fixed order in f64, so all k copies of the
 //     chain state stay bit-identical without any broadcast;
+//     the lean kernels of <= 8 coefficients lay a record out in 16-byte PAIRS of granules and poll it
+//     with four 16-byte sc1 loads per round instead of eight 8-byte ones, then swap the halves back
+//     into the same lanes and the same order of the sums (BL_POLL_PAIRS, below; what it measured:
+//     profiles/NOTES.md, profiles/poll_pairs/);
 //   * the control wave (lane d = dimension d) then writes the SPECULATIVE next position -- the next
 //     leaf of the subtree or the first leaf of the next doubling, a few FMAs from the gathered
 //     gradient -- and releases the compute waves; NumPyro's per-leaf decisions (finish the
@@ -225,6 +229,25 @@ struct BlSpinBound {
 #define BL_RESIDENT_MAX_FLOATS 96
 #endif
 #define SMALL_D_NVP(LEAN, MODEL, KS, KO) ((LEAN) && ((MODEL) == 0 || (MODEL) == 1) && (KS) + (KO) + 2 <= 8)
+// Paired records (the lean kernels of <= 8 coefficients: 16 granules per record, one-batch poll).  To halve the load instructions of a
+// poll round (measured: profiles/NOTES.md) the record is laid out for 16-byte loads: the value of granule v sits at position
+// pos(v) = v < 8 ? 2 v : 2 (v - 8) + 1, i.e. every aligned 16-byte pair holds {granule d, granule d + 8}, each half still its own 8-byte
+// {epoch, value} granule written by ONE 8-byte store (publisher unchanged but for the position).  The poller's lane (h = lane >> 5,
+// sub = (lane >> 3) & 3, c2 = lane & 7) reads pair c2 of record 4 (2 q' + h) + sub with ONE buffer_load_dwordx4 sc1, q' = 0 ... 3: four
+// loads per round cover the 32 record lines that eight 8-byte loads covered.  Both tags of every load are checked in place; behind a
+// complete round one v_permlane32_swap per load hands lanes 0-31 the granules 0-7 of the records 4 q + sub, q = 0 ... 7 in order, and
+// lanes 32-63 the granules 8-15 of the same records -- so every lane runs the SAME f64 chain over q as the 8-byte form, and the four
+// sub rows fold as (s0 + s1) + (s2 + s3) as before (lanes ^ 8 by DPP, lanes ^ 16 by v_permlane16_swap).  Granule v's total then
+// sits in lane bl_pair_lane(v): the gradient in lanes 0-7 as the decisions expect, granules 8-11 (with 8 coefficients the log-lik, the
+// abort flag and the two census words) in lanes 32-35.  Every other instantiation -- the general kernel among them, the bit-exact
+// reference of tests/test_gpu_poll_pairs.py -- keeps the 8-byte form.  0: the 8-byte form everywhere (A/B); publisher and poller
+// follow the one switch.  The host keeps the records' pitch even (biolith_hip.hip), so pairs stay 16-byte aligned.
+#ifndef BL_POLL_PAIRS
+#define BL_POLL_PAIRS 1
+#endif
+__host__ __device__ __forceinline__ constexpr int bl_pair_pos(int v) { return v < 8 ? 2 * v : 2 * (v - 8) + 1; }
+__host__ __device__ __forceinline__ constexpr int bl_pair_lane(int v) { return v < 8 ? v : 24 + v; }
+typedef unsigned BlU4 __attribute__((ext_vector_type(4)));
 #ifndef BL_GRP_FORM
 #define BL_GRP_FORM 2 // what the sampler's GRP instantiation carries: 2 = the lane-group evaluator alone, 1 = both evaluators (A/B)
 #endif
@@ -357,6 +380,21 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
     }
     const int nq = (p.k + G - 1) / G; // loads per round actually needed (<= 8 when k <= 8 G)
     const bool one_batch = LEAN || p.k <= 8 * G;
+    // paired records (BL_POLL_PAIRS): the 16-byte loads of this lane, and after the round's swaps the records 4 q + (lane >> 3 & 3)
+    constexpr bool PAIRS = BL_POLL_PAIRS && SMALL_D_NVP(LEAN, MODEL, KS, KO) && multi_wg;
+    unsigned ppoff[4] = {0u, 0u, 0u, 0u};
+    // (behind the exchange's fold the total of granule v -- D ... D + 3: log-lik, abort flag, census words -- is read from lane XL(v))
+#define BL_XL(v) (PAIRS ? bl_pair_lane(v) : (v))
+    if constexpr (PAIRS) {
+        const int psub = (lane >> 3) & 3;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int w = 4 * (2 * q + (lane >> 5)) + psub;
+            ppoff[q] = (unsigned)(((w < p.k ? w : p.k - 1) * p.pitch + 2 * (lane & 7)) * 8);
+        }
+#pragma unroll
+        for (int q = 0; q < 8; q++) pval[q] = (4 * q + psub < p.k) ? 1.0f : 0.0f;
+    }
 
     if (wave == 0) {
         S = cold->num_samples; W = cold->num_warmup; total = W + S;
@@ -523,8 +561,8 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
         have_pending = false;
         const double acc = p_acc;
         const float cg = p_cg, pe2 = p_pe2;
-        const double ll_tot = bl_readlane_d(acc, D);
-        const bool abort_req = bl_readlane_d(acc, D + 1) != 0.0;
+        const double ll_tot = bl_readlane_d(acc, BL_XL(D));
+        const bool abort_req = bl_readlane_d(acc, BL_XL(D + 1)) != 0.0;
         flag = 0;
         if (p_timed_out) flag = 4;     // BL_ERR_TIMEOUT
         else if (abort_req) flag = 5;  // BL_ERR_ABORTED
@@ -768,7 +806,8 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
                     // address was spilled to scratch by the fullest instantiations and reloaded on every publish)
                     int lane_o = lane;
                     asm volatile("" : "+v"(lane_o));
-                    const unsigned store_off = (unsigned)((member * p.pitch + (lane_o & (nvp - 1))) * 8);
+                    const int gran = lane_o & (nvp - 1);
+                    const unsigned store_off = (unsigned)((member * p.pitch + (PAIRS ? bl_pair_pos(gran) : gran)) * 8);
                     unsigned long long *dst = reinterpret_cast<unsigned long long *>(const_cast<unsigned char *>(rbase) + store_off);
                     if (local_c) // line stays in this XCD's L2, where every consumer of this chain polls it
                         __hip_atomic_store(dst, granule, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -900,6 +939,44 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
                 if (lane == D + 1 && (epoch & 255u) == 0u) // the host's abort request (fit(timeout=...))
                     comp = (__hip_atomic_load(cold->abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) ? 1.0f : 0.0f;
                 acc = (double)comp;
+            } else if (PAIRS) {
+                // paired records: four 16-byte sc1 loads per lane and round (see BL_POLL_PAIRS); loads beyond ceil(nq / 2) would only
+                // re-read record k - 1 and are skipped wave-uniformly (their tags pass, their values meet pval = 0)
+                const int nqp = (nq + 1) >> 1;
+                const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(xbase), (short)0, (int)(BL_XCHG_SLOTS * rec_bytes), 0x00020000);
+                const int soff = (int)((epoch & (BL_XCHG_SLOTS - 1u)) * rec_bytes);
+                BlU4 v[4];
+                BlSpinBound bound;
+                while (true) {
+#ifdef BL_STAMPS
+                    const long long st_r0 = (long long)clock64();
+#endif
+                    asm volatile("" ::: "memory"); // (compiler only: every round loads anew)
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        if (q < nqp) v[q] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)ppoff[q], soff, 16); // (aux 16: sc1)
+                        else v[q] = BlU4{0u, epoch, 0u, epoch};
+                    }
+                    unsigned bad = 0u;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) bad |= (v[q].y ^ epoch) | (v[q].w ^ epoch);
+                    const bool all_in = __all(bad == 0u);
+#ifdef BL_STAMPS
+                    st_sub[3] += (long long)clock64() - st_r0; // cycles in poll rounds (loads issued -> tags checked)
+#endif
+                    if (all_in) break;
+                    if (bound.expired(p.spin_limit)) { timed_out = true; break; }
+                    if (!local)
+                        for (int z = 0; z < p.poll_sleep; z++) __builtin_amdgcn_s_sleep(1);
+                }
+                BL_COUNT_SPINS(bound.spins)
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    // lanes 0-31: granules 0-7 of the records 4 (2 q) + sub and 4 (2 q + 1) + sub; lanes 32-63: their granules 8-15
+                    const auto r = __builtin_amdgcn_permlane32_swap(v[q].x, v[q].z, false, false);
+                    acc += (double)(pval[2 * q] * __uint_as_float(r[0]));
+                    acc += (double)(pval[2 * q + 1] * __uint_as_float(r[1]));
+                }
             } else if (one_batch) {
                 // common shape: one round of <= 8 loads per lane covers all k records.  (Measured and dropped: two rounds in flight
                 // half a round trip apart, the first complete one taken -- 4-11 % slower: the waits on the second round's loads
@@ -982,13 +1059,16 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
             }
             // fold the 64/nvp lane groups (each summed a different subset of the workgroups): element-wise
             // across rows, by gfx950's v_permlane16_swap / v_permlane32_swap (one VALU op per 32-bit half)
-            if (multi_wg) {
+            if (PAIRS) { // (s0 + s1) + (s2 + s3), as below: the sub rows are 8 lanes apart, the halves hold different granules
+                acc += bl_dpp_d<0x128, 0xF>(acc); // row_ror:8 = lanes ^ 8
+                acc = bl_fold_rows16_d(acc);
+            } else if (multi_wg) {
                 if (nvp <= 16) acc = bl_fold_rows16_d(acc);
                 if (nvp <= 32) acc = bl_fold_halves32_d(acc);
             }
             BL_STAMP(3)
             if (epoch == 1u && p.allow_local) {
-                const double sx = bl_readlane_d(acc, D + 2), sxx = bl_readlane_d(acc, D + 3);
+                const double sx = bl_readlane_d(acc, BL_XL(D + 2)), sxx = bl_readlane_d(acc, BL_XL(D + 3));
                 local = ((double)p.k * sxx == sx * sx); // exact: small integers
                 if (lane == 0) sh_flag[1] = local ? 1 : 0; // (the compute waves' stores from the next evaluation on)
             }
