@@ -27,6 +27,7 @@
 #include "count_posterior.hpp"
 #include "comb_predict.hpp"
 #include "predictive_check.hpp"
+#include "predictive_check_counts.hpp"
 #include "predictive_density.hpp"
 #include "psis_loo.hpp"
 
@@ -694,6 +695,57 @@ extern "C" int bl_predictive_check(bl_dataset *ds, int n_draws, const float *dra
                             {nullptr, by_revisit ? nb * TJ * 8 : 0, (void **)&p.visit_exp, true},
                             {nullptr, by_revisit ? nb * TJ * 4 : 0, (void **)&p.visit_rep, true}};
     return run_over_draws(ds, n_draws, draws, std::max<size_t>(32, nb * std::max(32, TJ * 8)), outs, p, bl_launch_predictive_check);
+}
+
+// ---- the same check for the abundance and count models: occu_rn, nmixture, occu_cop ----
+// (BUILDER-DEFINED: the reference's check is occu's.)  Kernels: predictive_check_counts.hip.  They regenerate bl_predict's (occu_rn) /
+// bl_predict_counts' (nmixture, occu_cop) replicate and bl_deterministic's sites, so they read what those read: the head of the handle's
+// rows, the raw observation covariates and occu_cop's raw durations.  The observed counts come from the caller; their total per revisit
+// does not depend on the draw and is formed here.  The blocks' partials are workspace of the draws' chunk; the results are 32 bytes a draw.
+extern "C" int bl_predictive_check_counts(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, const int32_t *obs,
+                                          double *by_site, double *by_revisit)
+{
+    int rc = per_draw_front("bl_predictive_check_counts", ds, n_draws, draws, obs && (by_site || by_revisit),
+                            [](const bl_dataset *d) {
+                                return d->nsp == 1 && (d->model == 1 || d->model == 3 || d->model == 4 || re_kind_in(d, {3, 4, 5, 6, 7}));
+                            },
+                            "occu_rn, nmixture and occu_cop, with or without a false-positive rate / random effects; occu uses bl_predictive_check");
+    if (rc || (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
+    const int model = branch_model(ds);
+    if (model == 3 && (rc = upload_once(&ds->d_dur, ds->h_dur))) return rc; // occu_cop's session durations
+    const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates, TJ = T * J;
+    std::vector<double> obs_visit((size_t)TJ, 0.0);
+    for (int j = 0; j < J; j++)
+        for (int t = 0; t < T; t++) {
+            const int32_t *row = obs + ((size_t)j * T + t) * N;
+            int64_t c = 0;
+            for (int i = 0; i < N; i++) {
+                if (row[i] < -1) return bl_fail(BL_ERR_INVALID, "bl_predictive_check_counts: obs holds %d (a count, or -1 = not observed)", (int)row[i]);
+                if (row[i] > 1 && model == 1)
+                    return bl_fail(BL_ERR_INVALID, "bl_predictive_check_counts: obs holds %d (occu_rn: 0, 1, or -1 = not observed)", (int)row[i]);
+                c += row[i] > 0 ? row[i] : 0;
+            }
+            obs_visit[(size_t)t * J + j] = (double)c;
+        }
+    BlPredCheckCountsParams p{};
+    p.rows = ds->d_rows; p.wraw = ds->d_wraw; p.dur = ds->d_dur; p.ns = ds->n_stride; p.N = N; p.T = T; p.J = J; p.Ks = ds->Ks; p.Ko = ds->Ko;
+    p.D = ds->D; p.model = model; p.K = ds->max_abundance; p.seed = (unsigned long long)seed; p.c = draw_coords(ds);
+    p.n_blocks = (N + BL_PCC_THREADS - 1) / BL_PCC_THREADS;
+    DevScratch scratch;
+    int *d_obs = nullptr;
+    double *d_obs_visit = nullptr;
+    BL_HIP(scratch.alloc((void **)&d_obs, (size_t)TJ * N * 4));
+    BL_HIP(hipMemcpy(d_obs, obs, (size_t)TJ * N * 4, hipMemcpyHostToDevice));
+    BL_HIP(scratch.alloc((void **)&d_obs_visit, (size_t)TJ * 8));
+    BL_HIP(hipMemcpy(d_obs_visit, obs_visit.data(), (size_t)TJ * 8, hipMemcpyHostToDevice));
+    p.obs = d_obs; p.obs_visit = d_obs_visit;
+    const size_t nb = (size_t)p.n_blocks;
+    const DrawOut outs[] = {{by_site, 32, (void **)&p.by_site, false},
+                            {by_revisit, 32, (void **)&p.by_revisit, false},
+                            {nullptr, by_site ? nb * 32 : 0, (void **)&p.site_part, true},
+                            {nullptr, by_revisit ? nb * TJ * 8 : 0, (void **)&p.visit_exp, true},
+                            {nullptr, by_revisit ? nb * TJ * 8 : 0, (void **)&p.visit_rep, true}};
+    return run_over_draws(ds, n_draws, draws, std::max<size_t>(32, nb * std::max(32, TJ * 8)), outs, p, bl_launch_predictive_check_counts);
 }
 
 // ---- the information criteria's two reductions of the pointwise log-likelihood, fused ----

@@ -36,9 +36,9 @@ __global__ void bl_predict_kernel(const BlPredictParams p)
             if (!y) continue;
             for (int j = 0; j < J; j++) {
                 const float r = pm_sigmoid(pm_visit_nu(p.wraw, ns, th, al, Ko, c, T, J, t * J + j, i));
-                float pd = model == 1 ? 1.0f - __powf(1.0f - r, (float)zn) : (float)zn * r;
+                float pd = model == 1 ? pm_rn_detection(r, zn) : (float)zn * r;
                 if (model == 2) pd = pm_false_positives(pd, f_c, f_u, zn);
-                if (model == 1) pd = 1.0f - (1.0f - pd) * (1.0f - fpr); // (Royle-Nichols with a false-positive rate: occu_rn.py:214-221; fpr = 0 without)
+                if (model == 1) pd = pm_rn_false_positives(pd, fpr); // (Royle-Nichols with a false-positive rate: occu_rn.py:214-221; fpr = 0 without)
                 const float u = rng.uniform();
                 y[(((size_t)(n - p.n0) * J + j) * T + t) * N + i] = (u < pd) ? 1 : 0;
             }
@@ -46,31 +46,6 @@ __global__ void bl_predict_kernel(const BlPredictParams p)
     }
 }
 
-// Poisson(lam): inversion by sequential search for lam < 10, else Hoermann's PTRS transformed rejection
-// ("The transformed rejection method for generating Poisson random variables", 1993); both exact.
-__device__ inline int bl_poisson(BlPredRng &rng, double lam)
-{
-    if (!(lam > 0.0)) return 0;
-    if (lam < 10.0) {
-        const double enlam = exp(-lam);
-        int k = 0;
-        double prod = (double)rng.uniform();
-        while (prod > enlam && k < 1000) { prod *= (double)rng.uniform(); k++; }
-        return k;
-    }
-    const double slam = sqrt(lam), loglam = log(lam);
-    const double b = 0.931 + 2.53 * slam, a = -0.059 + 0.02483 * b;
-    const double invalpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2.0);
-    for (int it = 0; it < 1000; it++) {
-        const double U = (double)rng.uniform() - 0.5, V = (double)rng.uniform();
-        const double us = 0.5 - fabs(U);
-        const double kf = floor((2.0 * a / us + b) * U + lam + 0.43);
-        if (us >= 0.07 && V <= vr) return (int)kf;
-        if (kf < 0.0 || (us < 0.013 && V > us)) continue;
-        if (log(V) + log(invalpha) - log(a / (us * us) + b) <= -lam + kf * loglam - lgamma(kf + 1.0)) return (int)kf;
-    }
-    return (int)lam;
-}
 // occu_cop (occu_cop.py:222-255, obs withheld):  z ~ Bernoulli(psi),  y_j ~ Poisson(dur_j (z lambda_j + (1 - z) f_u + f_c))
 // nmixture (nmixture.py:183-220, obs withheld):  N ~ Poisson(lambda) restricted to 0..K,  y_j ~ Binomial(N, p_j)
 __global__ void bl_predict_counts_kernel(const BlPredictParams p)
@@ -86,7 +61,7 @@ __global__ void bl_predict_counts_kernel(const BlPredictParams p)
         const float *th = p.draws + (size_t)n * p.D;
         const float *al = th + Ks + 1;
         const float eta = pm_site_eta(x, 1, th, Ks, c, i);
-        const float f = c.fp_mode ? __expf(th[c.o_fp]) : 0.0f; // occu_cop's rate of false detections
+        const float f = c.fp_mode ? pm_cop_fp_rate(th[c.o_fp]) : 0.0f; // occu_cop's rate of false detections
         const float f_c = c.fp_mode == BL_FP_CONSTANT ? f : 0.0f, f_u = c.fp_mode == BL_FP_UNOCCUPIED ? f : 0.0f;
         for (int t = 0; t < T; t++) {
             BlPredRng rng = bl_cell_rng(p.seed, n, T, t, N, i);
@@ -100,8 +75,7 @@ __global__ void bl_predict_counts_kernel(const BlPredictParams p)
                 if (model == 4) {
                     cnt = bl_binomial(rng, zn, pm_sigmoid(nu)); // Binomial(N, p), N <= 127 (pred_rng.hpp)
                 } else {
-                    const double rate = (double)p.dur[(size_t)v * ns + i] * ((zn ? (double)__expf(nu) : (double)f_u) + (double)f_c);
-                    cnt = bl_poisson(rng, rate);
+                    cnt = bl_poisson(rng, pm_cop_rate(p.dur[(size_t)v * ns + i], zn, nu, f_u, f_c)); // (Poisson by inversion or PTRS: predict_math.hpp)
                 }
                 y[(((size_t)(n - p.n0) * J + j) * T + t) * N + i] = cnt;
             }

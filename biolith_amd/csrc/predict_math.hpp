@@ -1,7 +1,8 @@
 // predict_math.hpp -- the arithmetic of the posterior predictive, written once for every kernel that states it: predict.hip (bl_predict,
-// bl_predict_counts, bl_predict_scores, bl_deterministic), comb_predict.hip, predictive_check.hip and predictive_density.hip.  The last
-// two promise bl_predict's replicate and bl_deterministic's psi and p bit for bit, and -ffp-contract=on fuses per source expression:
-// they hold that promise by calling what bl_predict calls.  (The conditional posteriors' arithmetic is posterior_math.hpp.)
+// bl_predict_counts, bl_predict_scores, bl_deterministic), comb_predict.hip, predictive_check.hip, predictive_check_counts.hip and
+// predictive_density.hip.  The last three promise bl_predict's / bl_predict_counts' replicate and bl_deterministic's sites bit for bit,
+// and -ffp-contract=on fuses per source expression: they hold that promise by calling what the predict kernels call.  (The conditional
+// posteriors' arithmetic is posterior_math.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -63,6 +64,43 @@ __device__ __forceinline__ int pm_draw_abundance(BlPredRng &rng, float eta, int 
         p *= lam / (double)(m + 1);
     }
     return K;
+}
+// Royle-Nichols: a visit's detection probability 1 - (1 - r)^N among N individuals, then its constant false-positive rate on top
+// (occu_rn.py:214-221; fpr = 0 without one); an expression each
+__device__ __forceinline__ float pm_rn_detection(float r, int zn) { return 1.0f - __powf(1.0f - r, (float)zn); }
+__device__ __forceinline__ float pm_rn_false_positives(float pd, float fpr) { return 1.0f - (1.0f - pd) * (1.0f - fpr); }
+// occu_cop: the false-detection rate of the draw's coordinate phi = log(rate), and a visit's Poisson rate
+// dur (z exp(nu) + (1 - z) f_u + f_c)
+__device__ __forceinline__ float pm_cop_fp_rate(float phi) { return __expf(phi); }
+__device__ __forceinline__ double pm_cop_rate(float dur, int zn, float nu, float f_u, float f_c)
+{
+    return (double)dur * ((zn ? (double)__expf(nu) : (double)f_u) + (double)f_c);
+}
+// Poisson(lam): inversion by sequential search for lam < 10, else Hoermann's PTRS transformed rejection
+// ("The transformed rejection method for generating Poisson random variables", 1993); both exact.  The number of uniforms depends on
+// the data.
+__device__ inline int bl_poisson(BlPredRng &rng, double lam)
+{
+    if (!(lam > 0.0)) return 0;
+    if (lam < 10.0) {
+        const double enlam = exp(-lam);
+        int k = 0;
+        double prod = (double)rng.uniform();
+        while (prod > enlam && k < 1000) { prod *= (double)rng.uniform(); k++; }
+        return k;
+    }
+    const double slam = sqrt(lam), loglam = log(lam);
+    const double b = 0.931 + 2.53 * slam, a = -0.059 + 0.02483 * b;
+    const double invalpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2.0);
+    for (int it = 0; it < 1000; it++) {
+        const double U = (double)rng.uniform() - 0.5, V = (double)rng.uniform();
+        const double us = 0.5 - fabs(U);
+        const double kf = floor((2.0 * a / us + b) * U + lam + 0.43);
+        if (us >= 0.07 && V <= vr) return (int)kf;
+        if (kf < 0.0 || (us < 0.013 && V > us)) continue;
+        if (log(V) + log(invalpha) - log(a / (us * us) + b) <= -lam + kf * loglam - lgamma(kf + 1.0)) return (int)kf;
+    }
+    return (int)lam;
 }
 // a standard normal by Box-Muller: two uniforms, the first floored at 2^-24
 __device__ __forceinline__ float pm_normal(BlPredRng &rng)

@@ -508,6 +508,25 @@ class OccuDataset:
         fn = lambda h, n, d, s, *outs: self._lib.bl_predictive_check(h, n, d, s, o8.ctypes.data_as(C.POINTER(C.c_uint8)), *outs)
         return self._per_draw(fn, draws, seed, [(by_site, (4,), np.float64), (by_revisit, (4,), np.float64)], pinned=False)
 
+    def predictive_check_counts(self, draws, obs, seed: int = 0, by_site: bool = True, by_revisit: bool = True):
+        """``predictive_check`` for the abundance and count models (BUILDER-DEFINED): ``by_site`` and ``by_revisit``, each (n, 4) float64
+        = ``ft_obs, ft_rep, chi_obs, chi_rep`` or ``None``, for draws (n, D).  ``obs`` is (N, T, J): non-negative whole counts (occu_rn:
+        0 / 1), NaN = not observed.  The replicate is ``predictive(draws, seed)``'s ``y``; the expectation is the model's mean of ``y``
+        with the latent state summed out, from ``deterministic``'s float32 sites; neither is materialised.  occu_rn, nmixture and
+        occu_cop handles with or without a false-positive rate / random effects (include/biolith_hip.h: bl_predictive_check_counts)."""
+        o = np.asarray(obs, dtype=np.float64)
+        if o.shape != (self.N, self.T, self.J):
+            raise ValueError(f"obs must have shape (n_sites, n_periods, n_replicates) = {(self.N, self.T, self.J)}, got {o.shape}")
+        seen = ~np.isnan(o)
+        whole = o[seen]
+        if not (np.isfinite(whole).all() and (whole >= 0).all() and (whole == np.floor(whole)).all() and (whole < 2 ** 31).all()):
+            raise ValueError("obs must hold non-negative whole counts or NaN")
+        if self.model == "occu_rn" and (whole > 1).any():
+            raise ValueError("obs must hold 0, 1 or NaN (occu_rn)")
+        o32 = np.ascontiguousarray(np.where(seen, o, -1.0).astype(np.int32).transpose(2, 1, 0))   # (J, T, N)
+        fn = lambda h, n, d, s, *outs: self._lib.bl_predictive_check_counts(h, n, d, s, o32.ctypes.data_as(C.POINTER(C.c_int32)), *outs)
+        return self._per_draw(fn, draws, seed, [(by_site, (4,), np.float64), (by_revisit, (4,), np.float64)], pinned=False)
+
     def predictive_density(self, draws, obs, seed: int = 0, marginal: bool = False, per_draw: bool = True, point_lse: bool = True,
                            point_var: bool = True):
         """The pointwise log-likelihood of ``obs`` under draws (n, D), reduced on the device without being stored: ``per_draw`` (n,)

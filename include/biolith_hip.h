@@ -408,6 +408,27 @@ int bl_predictive_check(bl_dataset *ds, int n_draws, const float *draws, uint64_
                         double *by_revisit);
 
 /*
+ * The same check for the abundance and count models -- BUILDER-DEFINED, the reference's check being occu's: per posterior draw the
+ * discrepancy of the observed and of a replicate data set against the model's mean E of y with the latent state summed out.  The replicate
+ * is bl_predict's (occu_rn) / bl_predict_counts' (nmixture, occu_cop) y for the same seed, bit for bit: the cell's generator, the latent
+ * state first, then every visit in j order whether it is seen or not, the same arithmetic.  E is formed in float64 from the float32 sites
+ * of bl_deterministic (lambda = abundance, p = prob_detection, psi, rate = rate_detection), K = max_abundance:
+ *   nmixture  E = m p,  m = sum_n n w_n / sum_n w_n,  w_n = lambda^n / n!  over n = 0 .. K (the mean of the restricted Poisson)
+ *   occu_rn   E = 1 - (1 - f) sum_n w_n (1 - p)^n / sum_n w_n
+ *   occu_cop  E = session_duration (psi rate + (1 - psi) f_u + f_c)
+ * f (f_c if BL_FP_CONSTANT, f_u if BL_FP_UNOCCUPIED; 0 without a rate) is the float32 site value of the draw's coordinate phi:
+ * (float)(1 / (1 + exp(-(double)phi))) for occu_rn, (float)exp((double)phi) for occu_cop.  The sums are scaled as they run: finite for
+ * any float32 lambda (an infinite one reads as FLT_MAX); exp(-lambda) cancels and is not formed.  Statistics, groupings, output layout,
+ * fixed summation order (two calls return the same bits) and NULL handling are bl_predictive_check's; counts are summed in float64.
+ * obs is [J][T][N] int32 on the host: the observed count, -1 = not observed; a visit counts where obs >= 0 and by nothing else.  A value
+ * below -1, or above 1 on an occu_rn handle: BL_ERR_INVALID, the message holds the value.  Serves the one-species handles of
+ * bl_dataset_create_rn, _rn_re, _rn_fp, _nmix, _nmix_re, _cop, _cop_re; every other handle: BL_ERR_UNSUPPORTED, the message names the
+ * model (occu handles are pointed to bl_predictive_check).  BL_ERR_BUSY while a NUTS launch is in flight on the handle.
+ */
+int bl_predictive_check_counts(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, const int32_t *obs, double *by_site,
+                               double *by_revisit);
+
+/*
  * The information criteria's reductions of the pointwise log-likelihood (biolith/evaluation/log_likelihood.py:10-96 under lppd.py,
  * waic.py and deviance.py), fused: the log-likelihood ll of every observation under every posterior draw, [n_draws][J][T][N], is formed
  * on the device in float64 and reduced there -- over the points per draw, and over the draws per point -- without being stored.
