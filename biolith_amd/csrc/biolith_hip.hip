@@ -30,6 +30,7 @@
 #include "predictive_check_counts.hpp"
 #include "predictive_density.hpp"
 #include "psis_loo.hpp"
+#include "site_summary.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -2407,6 +2408,73 @@ extern "C" int bl_deterministic(bl_dataset *ds, int n_draws, const float *draws,
     const size_t cells = (size_t)p.T * p.N * 4; // per draw
     const DrawOut outs[] = {{psi, cells, (void **)&p.psi, false}, {prob_detection, cells * p.J, (void **)&p.prob, false}};
     return run_over_draws(ds, n_draws, draws, cells * (prob_detection ? (size_t)p.J : 1), outs, p, bl_launch_deterministic);
+}
+
+// ---- the deterministic sites' summary over the draws: mean, sd and order statistics per cell, fused ----
+// (No counterpart in the reference.)  Kernels: site_summary.hip.  They read what bl_deterministic's kernels read and every draw, and
+// write per cell: a launch per wanted site over all the draws, which goes out when they are up (run_over_draws's one chunk: nothing
+// here grows with the draws) and is done before run_over_draws lets go of them.
+extern "C" int bl_site_summary(bl_dataset *ds, int n_draws, const float *draws, int n_ranks, const int32_t *ranks, double *psi_mean,
+                               double *psi_sd, float *psi_order, double *prob_mean, double *prob_sd, float *prob_order)
+{
+    const bool first = psi_mean || psi_sd || psi_order, second = prob_mean || prob_sd || prob_order, order = psi_order || prob_order;
+    if (!ds || !draws || n_draws <= 0 || !(first || second)) return bl_fail(BL_ERR_INVALID, "bl_site_summary: bad argument");
+    if (ds->nsp > 1) return bl_fail(BL_ERR_UNSUPPORTED, "bl_site_summary: a joint-species handle samples; take the sites from one handle per species");
+    if (ds->model == 8) return bl_fail(BL_ERR_UNSUPPORTED, "bl_site_summary: the dynamic occupancy model's sites (psi, gamma, eps) are formed by the caller from the draws");
+    if (ds->model == 6 && ds->re.kind == 8)
+        return bl_fail(BL_ERR_UNSUPPORTED, "bl_site_summary: occu_comb's sites (psi, PC / ARU detection probabilities) are formed by the caller from the draws");
+    if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
+    if (order) {
+        if (n_ranks <= 0 || !ranks) return bl_fail(BL_ERR_INVALID, "bl_site_summary: an order output is wanted and n_ranks=%d", n_ranks);
+        if (n_ranks > BL_SUMMARY_MAX_RANKS)
+            return bl_fail(BL_ERR_UNSUPPORTED, "bl_site_summary: n_ranks=%d above BL_SUMMARY_MAX_RANKS=%d", n_ranks, BL_SUMMARY_MAX_RANKS);
+        for (int r = 0; r < n_ranks; r++)
+            if (ranks[r] < 0 || ranks[r] >= n_draws)
+                return bl_fail(BL_ERR_INVALID, "bl_site_summary: ranks[%d]=%d outside 0 .. n_draws - 1 = %d", r, (int)ranks[r], n_draws - 1);
+    }
+    int rc = set_device(ds);
+    if (rc || (second && (rc = upload_once(&ds->d_wraw, ds->h_wraw)))) return rc;
+    BlSiteSummaryParams p{};
+    p.rows = ds->d_rows; p.wraw = ds->d_wraw; p.ns = ds->n_stride;
+    p.N = ds->dims.n_sites; p.T = ds->dims.n_periods; p.J = ds->dims.n_replicates; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = ds->D;
+    p.model = branch_model(ds); p.c = draw_coords(ds); p.n_draws = n_draws;
+    p.n_ranks = order ? n_ranks : 0;
+    for (int r = 0; r < p.n_ranks; r++) p.ranks[r] = ranks[r];
+    const size_t sites = (size_t)p.N, visits = sites * p.T * p.J;
+    // one site's device outputs and the host arrays they go back to
+    struct Site {
+        size_t cells;
+        double *mean, *sd;
+        float *order;
+        double *d_mean = nullptr, *d_sd = nullptr;
+        float *d_order = nullptr;
+    } site[2] = {{sites, psi_mean, psi_sd, psi_order}, {visits, prob_mean, prob_sd, prob_order}};
+    DevScratch scratch;
+    for (Site &s : site) {
+        if (s.mean) BL_HIP(scratch.alloc((void **)&s.d_mean, s.cells * 8));
+        if (s.sd) BL_HIP(scratch.alloc((void **)&s.d_sd, s.cells * 8));
+        if (s.order) BL_HIP(scratch.alloc((void **)&s.d_order, s.cells * 4 * p.n_ranks));
+    }
+    void *none = nullptr;
+    const DrawOut outs[] = {{nullptr, 0, &none, false}}; // (nothing per draw)
+    rc = run_over_draws(ds, n_draws, draws, 0, outs, [&](const float *d_draws, int n0, int, int) {
+        if (n0 != 0) return hipSuccess;
+        p.draws = d_draws;
+        int e = 0;
+        for (int k = 0; k < 2 && !e; k++) {
+            p.mean = site[k].d_mean; p.sd = site[k].d_sd; p.order = site[k].d_order;
+            if (p.mean || p.sd || p.order) e = k ? bl_launch_site_summary_prob(&p, nullptr) : bl_launch_site_summary_psi(&p, nullptr);
+        }
+        if (!e) e = (int)hipStreamSynchronize(nullptr);
+        return (hipError_t)e;
+    });
+    if (rc) return rc;
+    for (const Site &s : site) {
+        if (s.mean) BL_HIP(hipMemcpy(s.mean, s.d_mean, s.cells * 8, hipMemcpyDeviceToHost));
+        if (s.sd) BL_HIP(hipMemcpy(s.sd, s.d_sd, s.cells * 8, hipMemcpyDeviceToHost));
+        if (s.order) BL_HIP(hipMemcpy(s.order, s.d_order, s.cells * 4 * p.n_ranks, hipMemcpyDeviceToHost));
+    }
+    return BL_OK;
 }
 
 // ------------------------------------------------------- multi-GPU: the gather of the draws over RCCL ----

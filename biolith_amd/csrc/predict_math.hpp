@@ -1,7 +1,7 @@
 // predict_math.hpp -- the arithmetic of the posterior predictive, written once for every kernel that states it: predict.hip (bl_predict,
 // bl_predict_counts, bl_predict_scores, bl_deterministic), comb_predict.hip, predictive_check.hip, predictive_check_counts.hip and
-// predictive_density.hip.  The last three promise bl_predict's / bl_predict_counts' replicate and bl_deterministic's sites bit for bit,
-// and -ffp-contract=on fuses per source expression: they hold that promise by calling what the predict kernels call.  (The conditional
+// predictive_density.hip, and site_summary.hip.  The last four promise bl_predict's / bl_predict_counts' replicate and bl_deterministic's
+// sites bit for bit, and -ffp-contract=on fuses per source expression: they hold that promise by calling what the predict kernels call.  (The conditional
 // posteriors' arithmetic is posterior_math.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,14 +33,24 @@ __device__ __forceinline__ float pm_visit_linear(const float *__restrict__ wraw,
 {
     return pm_linear(wraw + ((size_t)v * Ko * ns + i), ns, al, Ko);
 }
-// the visit predictor nu of visit v = t J + j at site i: alpha . (1, w), the site's detection effect and the visit's effect
-__device__ __forceinline__ float pm_visit_nu(const float *__restrict__ wraw, int ns, const float *__restrict__ th, const float *__restrict__ al,
-                                             int Ko, const BlDrawCoords &c, int T, int J, int v, int i)
+// what joins alpha . (1, w) of visit v = t J + j at site i: the site's detection effect and the visit's effect
+__device__ __forceinline__ float pm_visit_effects(float nu, const float *__restrict__ th, const BlDrawCoords &c, int T, int J, int v, int i)
 {
-    float nu = pm_visit_linear(wraw, ns, al, Ko, v, i);
     if (c.o_v >= 0) nu += th[c.o_v + i];
     if (c.o_e >= 0) nu += th[c.o_e + (size_t)i * T * J + v];
     return nu;
+}
+// the visit predictor nu of visit v = t J + j at site i: alpha . (1, w) and the effects
+__device__ __forceinline__ float pm_visit_nu(const float *__restrict__ wraw, int ns, const float *__restrict__ th, const float *__restrict__ al,
+                                             int Ko, const BlDrawCoords &c, int T, int J, int v, int i)
+{
+    return pm_visit_effects(pm_visit_linear(wraw, ns, al, Ko, v, i), th, c, T, J, v, i);
+}
+// the same with the visit's covariates staged in registers, w[k] = wraw[(v Ko + k) ns + i]
+__device__ __forceinline__ float pm_visit_nu_staged(const float *__restrict__ w, const float *__restrict__ th, const float *__restrict__ al,
+                                                    int Ko, const BlDrawCoords &c, int T, int J, int v, int i)
+{
+    return pm_visit_effects(pm_linear(w, 1, al, Ko), th, c, T, J, v, i);
 }
 // a detection probability pd under false positives: f_c acts on every site, f_u on unoccupied ones (ONE expression: it contracts as one)
 __device__ __forceinline__ float pm_false_positives(float pd, float f_c, float f_u, int zn)

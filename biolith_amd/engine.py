@@ -467,6 +467,34 @@ class OccuDataset:
         _PINNED.kick(self._lib)
         return out_psi, out_pd
 
+    def site_summary(self, draws, ranks=(), psi: bool = True, prob_detection: bool = True):
+        """The deterministic sites' summary over draws (n, D), fused on the device (BUILDER-DEFINED): ``psi_mean, psi_sd, psi_order,
+        prob_mean, prob_sd, prob_order``.  The first site (``psi``; occu_rn, nmixture: ``abundance``) is constant over the periods and
+        comes back per site: mean and sd (N,) float64, order (len(ranks), N) float32; the second (``prob_detection``; occu_cop:
+        ``rate_detection``): (J, T, N) and (len(ranks), J, T, N).  ``order[r]`` is the value of rank ``ranks[r]`` (0 = smallest) among
+        the cell's n float32 values of ``deterministic``, bit for bit; mean and sd (ddof 1, NaN for one draw) are float64 sums over them
+        in draw order.  ``None`` for a site that is not wanted, and for the order statistics without ranks.  Nothing of size (n, T, N)
+        or (n, J, T, N) exists on the device or the host.  Draws must be finite (include/biolith_hip.h: bl_site_summary)."""
+        d = self._draw_matrix(draws)
+        n = d.shape[0]
+        r = np.ascontiguousarray(np.asarray(ranks, dtype=np.int64).reshape(-1))
+        if not (psi or prob_detection):
+            raise ValueError("site_summary(): neither site is wanted")
+        if n == 0:
+            raise ValueError("site_summary(): no draws")
+        if r.size > _ffi.SUMMARY_MAX_RANKS:
+            raise NotImplementedError(f"site_summary(): {r.size} ranks, at most {_ffi.SUMMARY_MAX_RANKS} (BL_SUMMARY_MAX_RANKS)")
+        if r.size and (r.min() < 0 or r.max() >= n):
+            raise ValueError(f"site_summary(): ranks must lie in 0 .. n_draws - 1 = {n - 1}")
+        r32 = r.astype(np.int32)
+        out = []
+        for want, shape in ((psi, (self.N,)), (prob_detection, (self.J, self.T, self.N))):
+            out += [np.empty(shape) if want else None, np.empty(shape) if want else None,
+                    np.empty((r.size,) + shape, dtype=np.float32) if want and r.size else None]
+        ptrs = [None if a is None else a.ctypes.data_as(C.POINTER(_CTYPE[a.dtype.type])) for a in out]
+        _ffi.check(self._lib.bl_site_summary(self._h, n, _fp(d), int(r.size), r32.ctypes.data_as(C.POINTER(C.c_int32)), *ptrs))
+        return tuple(out)
+
     def _per_draw(self, fn, draws, seed, outs, pinned=True):
         """Calls a per-draw entry ``fn(handle, n, draws, seed, *outputs)`` for draws (n, D).  ``outs`` lists (wanted, shape behind
         the draw axis, dtype) per output; returns the arrays, ``None`` where not wanted.  With ``pinned`` the 4-byte outputs come from

@@ -341,6 +341,29 @@ int bl_nuts_debug_counters(bl_dataset *ds, int64_t *out /*[n<=544]*/, int n);
 int bl_deterministic(bl_dataset *ds, int n_draws, const float *draws, float *psi, float *prob_detection);
 
 /*
+ * The summary of the deterministic sites over the posterior draws, fused -- BUILDER-DEFINED (the reference's users reduce predict()'s
+ * arrays on the host): per cell of bl_deterministic's two sites, over all n_draws draws, without the arrays [n_draws][T][N] and
+ * [n_draws][J][T][N] ever being stored.  With v_0 .. v_{n-1} the cell's float32 values of bl_deterministic, bit for bit, in draw order:
+ *   mean   = (sum_n v_n) / n_draws, summed in float64 in draw order
+ *   sd     = sqrt(sum_n (v_n - mean)^2 / (n_draws - 1)), float64, in draw order; NaN for n_draws == 1
+ *   order  [r] = the float32 value of rank ranks[r] (0 = the smallest) in the sorted order of the cell's values, bit for bit
+ * The first site (psi; occu_rn, nmixture: abundance) is constant over the periods and comes back per site: psi_mean, psi_sd [N],
+ * psi_order [n_ranks][N].  The second (prob_detection; occu_cop: rate_detection): prob_mean, prob_sd [J][T][N], prob_order
+ * [n_ranks][J][T][N].  float64 / float32 on the host, NULL = skip (all six NULL: BL_ERR_INVALID); the kernel of a site none of whose
+ * outputs is wanted is not launched, and a skipped output never changes another.  ranks holds n_ranks values in 0 .. n_draws - 1, in any
+ * order, duplicates allowed; it is read only if an order output is wanted (then n_ranks <= 0 or a rank outside the range:
+ * BL_ERR_INVALID; n_ranks > BL_SUMMARY_MAX_RANKS: BL_ERR_UNSUPPORTED, the message names the cap).  n_draws itself is not limited.
+ * Both sites are >= 0 (a sigmoid or an exponential), so the order statistics are selected on the unsigned bit pattern of the values; a
+ * NaN value has no place in that order: NaN draws are not served (the caller keeps non-finite draws out; what comes back for a cell
+ * that met one is unspecified).  Every sum runs in a fixed order, no atomics: a cell's outputs are a function of its covariates, its
+ * effects and the draws alone, and two calls return the same bits.  Serves what bl_deterministic serves, with its refusals
+ * (BL_ERR_UNSUPPORTED: a joint-species handle, occu_dyn, occu_comb; BL_ERR_BUSY while a NUTS launch is in flight on the handle).
+ */
+#define BL_SUMMARY_MAX_RANKS 16
+int bl_site_summary(bl_dataset *ds, int n_draws, const float *draws, int n_ranks, const int32_t *ranks, double *psi_mean, double *psi_sd,
+                    float *psi_order, double *prob_mean, double *prob_sd, float *prob_order);
+
+/*
  * Posterior predictive draws of the discrete sites, one per posterior draw -- what
  * numpyro.infer.Predictive(model_fn, posterior_samples)(key, site_covs, obs_covs) samples in
  * biolith/utils/predict.py:66-92 (obs withheld, so no observation is masked):
