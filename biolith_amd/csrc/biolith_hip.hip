@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -31,6 +32,7 @@
 #include "predictive_density.hpp"
 #include "psis_loo.hpp"
 #include "site_summary.hpp"
+#include "regional_totals.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -2475,6 +2477,69 @@ extern "C" int bl_site_summary(bl_dataset *ds, int n_draws, const float *draws, 
         if (s.order) BL_HIP(hipMemcpy(s.order, s.d_order, s.cells * 4 * p.n_ranks, hipMemcpyDeviceToHost));
     }
     return BL_OK;
+}
+
+// ---- totals over regions: per draw the weighted total of the first site and of the latent state per region, fused ----
+// (No counterpart in the reference.)  Kernels: regional_totals.hip.  They read the site covariates at the head of the handle's rows and
+// nothing else of it, so nothing is uploaded but the slots: the site indices stable-sorted by region, every region padded to whole
+// 64-lane waves (regional_totals.hpp).  run_over_draws cuts the draws so that the workspace and the chunk's totals stay within its 256 MB
+// each (BL_TOTALS_WORKSPACE_BYTES says so in the header).
+static_assert(BL_TOTALS_WORKSPACE_BYTES == (256u << 20), "bl_regional_totals states run_over_draws' bound");
+extern "C" int bl_regional_totals(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, int n_regions, const int32_t *region,
+                                  const double *weight, double *site_total, double *latent_total)
+{
+    int rc = per_draw_front("bl_regional_totals", ds, n_draws, draws, (site_total || latent_total) && region,
+                            [](const bl_dataset *d) {
+                                return d->nsp == 1 && ((d->model >= 0 && d->model <= 4) || re_kind_in(d, {0, 1, 2, 3, 4, 5, 6, 7}));
+                            },
+                            "occu, occu_cs, occu_cop, occu_rn and nmixture: the handles of bl_predict, bl_predict_counts and bl_predict_scores");
+    if (rc) return rc;
+    const int N = ds->dims.n_sites, T = ds->dims.n_periods, G = n_regions;
+    if (G < 1) return bl_fail(BL_ERR_INVALID, "bl_regional_totals: n_regions=%d, at least 1", G);
+    std::vector<int> wave_first((size_t)G + 1, 0);
+    for (int i = 0; i < N; i++) {
+        if (region[i] < -1 || region[i] >= G)
+            return bl_fail(BL_ERR_INVALID, "bl_regional_totals: region[%d]=%d outside -1 .. n_regions - 1 = %d", i, (int)region[i], G - 1);
+        if (weight && !std::isfinite(weight[i])) return bl_fail(BL_ERR_INVALID, "bl_regional_totals: weight[%d]=%g is not finite", i, weight[i]);
+        if (region[i] >= 0) wave_first[(size_t)region[i] + 1]++; // (the region's sites for now)
+    }
+    if ((size_t)N + (size_t)63 * G > (size_t)INT_MAX)
+        return bl_fail(BL_ERR_UNSUPPORTED, "bl_regional_totals: %d sites in %d regions need more than 2^31 slots", N, G);
+    for (int g = 0; g < G; g++) wave_first[(size_t)g + 1] = wave_first[g] + (wave_first[(size_t)g + 1] + 63) / 64;
+    const int W = wave_first[G];
+    std::vector<int> slot_site((size_t)W * 64, -1), cursor(G);
+    std::vector<double> slot_w(weight ? (size_t)W * 64 : 0, 0.0);
+    for (int g = 0; g < G; g++) cursor[g] = wave_first[g] * 64;
+    for (int i = 0; i < N; i++) { // (in site order: a stable sort by region)
+        if (region[i] < 0) continue;
+        const int s = cursor[region[i]]++;
+        slot_site[s] = i;
+        if (weight) slot_w[s] = weight[i];
+    }
+
+    BlRegionalTotalsParams p{};
+    p.rows = ds->d_rows; p.ns = ds->n_stride; p.N = N; p.T = T; p.Ks = ds->Ks; p.D = ds->D;
+    p.model = branch_model(ds); p.scores = re_kind_in(ds, {1}); p.K = ds->max_abundance; p.c = draw_coords(ds);
+    p.seed = (unsigned long long)seed;
+    p.n_slots = W * 64; p.n_waves = W; p.n_regions = G;
+    p.site_rows = site_total ? 1 : 0; p.latent_rows = latent_total ? T : 0;
+    DevScratch scratch;
+    int *d_site = nullptr, *d_first = nullptr;
+    double *d_w = nullptr;
+    BL_HIP(scratch.alloc((void **)&d_site, slot_site.size() * 4));
+    BL_HIP(scratch.alloc((void **)&d_first, wave_first.size() * 4));
+    BL_HIP(hipMemcpy(d_site, slot_site.data(), slot_site.size() * 4, hipMemcpyHostToDevice));
+    BL_HIP(hipMemcpy(d_first, wave_first.data(), wave_first.size() * 4, hipMemcpyHostToDevice));
+    if (weight) {
+        BL_HIP(scratch.alloc((void **)&d_w, slot_w.size() * 8));
+        BL_HIP(hipMemcpy(d_w, slot_w.data(), slot_w.size() * 8, hipMemcpyHostToDevice));
+    }
+    p.slot_site = d_site; p.slot_w = d_w; p.wave_first = d_first;
+    const size_t rows = (size_t)p.site_rows + p.latent_rows;
+    const DrawOut outs[] = {{site_total, (size_t)G * 8, (void **)&p.site_total, false},
+                            {latent_total, (size_t)T * G * 8, (void **)&p.latent_total, false},
+                            {nullptr, rows * W * 8, (void **)&p.part, true}};
+    return run_over_draws(ds, n_draws, draws, rows * std::max(W, G) * 8, outs, p, bl_launch_regional_totals);
 }
 
 // ------------------------------------------------------- multi-GPU: the gather of the draws over RCCL ----

@@ -495,6 +495,30 @@ class OccuDataset:
         _ffi.check(self._lib.bl_site_summary(self._h, n, _fp(d), int(r.size), r32.ctypes.data_as(C.POINTER(C.c_int32)), *ptrs))
         return tuple(out)
 
+    def regional_totals(self, draws, region, n_regions: int, weight=None, seed: int = 0, site: bool = True, latent: bool = True):
+        """Per draw of draws (n, D) and region, the weighted totals of the first deterministic site and of the latent state, fused on
+        the device (BUILDER-DEFINED): ``site_total`` (n, n_regions) and ``latent_total`` (n, T, n_regions), float64, ``None`` where not
+        wanted.  ``region`` (N,) holds 0 .. n_regions - 1, -1 = in no region; ``weight`` (N,) finite float64, ``None`` = 1.  The terms
+        are ``deterministic``'s float32 first site and ``predictive``'s / ``predictive_scores``' latent state for the same ``seed``,
+        bit for bit, times the weight in float64, summed in one fixed order (include/biolith_hip.h: bl_regional_totals).  Nothing of
+        size (n, T, N) exists on the device or the host."""
+        d = self._draw_matrix(draws)
+        n = d.shape[0]
+        r = np.ascontiguousarray(np.asarray(region).reshape(-1), dtype=np.int32)
+        w = None if weight is None else np.ascontiguousarray(np.asarray(weight, dtype=np.float64).reshape(-1))
+        if not (site or latent):
+            raise ValueError("regional_totals(): neither total is wanted")
+        if n == 0:
+            raise ValueError("regional_totals(): no draws")
+        if r.size != self.N or (w is not None and w.size != self.N):
+            raise ValueError(f"regional_totals(): region and weight hold one entry per site ({self.N})")
+        G = int(n_regions)
+        out_site = np.empty((n, G)) if site else None
+        out_latent = np.empty((n, self.T, G)) if latent else None
+        _ffi.check(self._lib.bl_regional_totals(self._h, n, _fp(d), C.c_uint64(int(seed) & (2 ** 64 - 1)), G,
+                                                r.ctypes.data_as(C.POINTER(C.c_int32)), _dp(w), _dp(out_site), _dp(out_latent)))
+        return out_site, out_latent
+
     def _per_draw(self, fn, draws, seed, outs, pinned=True):
         """Calls a per-draw entry ``fn(handle, n, draws, seed, *outputs)`` for draws (n, D).  ``outs`` lists (wanted, shape behind
         the draw axis, dtype) per output; returns the arrays, ``None`` where not wanted.  With ``pinned`` the 4-byte outputs come from

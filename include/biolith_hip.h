@@ -364,6 +364,36 @@ int bl_site_summary(bl_dataset *ds, int n_draws, const float *draws, int n_ranks
                     float *psi_order, double *prob_mean, double *prob_sd, float *prob_order);
 
 /*
+ * The posterior of totals over sets of sites, fused -- BUILDER-DEFINED (the reference's users form predict()'s arrays and sum them on
+ * the host): per posterior draw and region, the weighted total of the first deterministic site and of the latent state, without the
+ * arrays [n_draws][T][N] ever being stored.  region[i] in 0 .. n_regions - 1 is site i's region, -1 = in no region; weight[i] is finite
+ * and may be zero or negative, NULL = 1.  With v_i(n) bl_deterministic's float32 value of the first site (psi; occu_rn, nmixture:
+ * abundance; it is constant over the periods) and z_{t,i}(n) the latent state bl_predict / bl_predict_counts / bl_predict_scores draw
+ * for the same seed (z; occu_rn, nmixture: N_i), both bit for bit:
+ *   site_total  [n][g]    = sum_{i in g} weight_i * (double) v_i(n)           [n_draws][n_regions]
+ *   latent_total[n][t][g] = sum_{i in g} weight_i * (double) z_{t,i}(n)       [n_draws][T][n_regions]
+ * float64 on the host, NULL = skip (both NULL: BL_ERR_INVALID); a skipped output never changes the other one, and with latent_total
+ * NULL no generator is touched.  A region without a site comes back 0.
+ * Order.  Every product is formed in float64 and the sums run in float64 in one fixed order, no atomics: region g's sites in site order
+ * are cut into runs of 64, the last run filled up with -0.0 (the identity of the sum: a region of one site returns its term's bits); a
+ * run is summed as the tree (x_l + x_{l+32}), then lanes 16, 8, 4, 2, 1 apart, and the runs' sums are added in run order.  Row g is
+ * therefore a function of region g's own sites in site order, their weights and the draws: it is the same bytes when the other sites
+ * are relabelled, merged into other regions or left out with -1, however the draws are chunked, and two calls return the same bytes.
+ * Workspace.  The device holds one double per (draw of a chunk, output row, run of 64) and per (draw of a chunk, output row, region),
+ * 1 + T output rows a draw; the draws go through in chunks such that each of the two is at most BL_TOTALS_WORKSPACE_BYTES -- or one
+ * draw's rows, should they alone be larger --, whatever n_draws is.  Next to it: the draws, and 16 bytes per run's 64 slots.  The padded
+ * runs cost at most 63 idle lanes per region: one region per site is served, at one wave of 64 lanes per site, which is wasteful.
+ * region or weight refused (BL_ERR_INVALID; the message holds the offending value): a label outside -1 .. n_regions - 1, a non-finite
+ * weight; also n_regions < 1.  Both outputs are untouched on any refusal.  Serves what bl_predict, bl_predict_counts and
+ * bl_predict_scores serve together -- occu, occu_cs, occu_cop, occu_rn, nmixture, with or without a false-positive rate / random
+ * effects --; occu_comb, occu_dyn and a joint-species handle: BL_ERR_UNSUPPORTED, the message names the model.  BL_ERR_BUSY while a NUTS
+ * launch is in flight on the handle.
+ */
+#define BL_TOTALS_WORKSPACE_BYTES (256u << 20)
+int bl_regional_totals(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, int n_regions, const int32_t *region,
+                       const double *weight, double *site_total, double *latent_total);
+
+/*
  * Posterior predictive draws of the discrete sites, one per posterior draw -- what
  * numpyro.infer.Predictive(model_fn, posterior_samples)(key, site_covs, obs_covs) samples in
  * biolith/utils/predict.py:66-92 (obs withheld, so no observation is masked):
