@@ -48,12 +48,19 @@
 // (make stamps); the shipped kernel executes none of this.
 #ifdef BL_STAMPS
 #define BL_STAMP_DECL long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long st_prev = (long long)clock64(); long long st_rt0 = (long long)wall_clock64(); long long st_spins = 0; \
-    long long st_kn[3] = {0, 0, 0}, st_kc[3] = {0, 0, 0}; int st_kind = 0; long long st_sub[6] = {0, 0, 0, 0, 0, 0}; long long st_t = 0;
-#define BL_STAMP(i) { const long long st_now = (long long)clock64(); st_acc[i] += st_now - st_prev; st_prev = st_now; }
+    long long st_kn[3] = {0, 0, 0}, st_kc[3] = {0, 0, 0}; int st_kind = 0; long long st_sub[6] = {0, 0, 0, 0, 0, 0}; long long st_t = 0; \
+    long long st_ae[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int st_ae_cls = -1;
+// The tick BEHIND a transition's end is a kind of its own (its stamp 0 is end_deferred alone): st_ae holds, for warm-up transitions
+// (class 0) and sampling ones (class 1), {ticks, stamp 0, stamp 1 = the wait for the compute waves, unsuccessful poll rounds}
+#define BL_STAMP(i) { const long long st_now = (long long)clock64(); st_acc[i] += st_now - st_prev; \
+    if (st_ae_cls >= 0 && (i) <= 1) { st_ae[st_ae_cls * 4 + 1 + ((i) & 1)] += st_now - st_prev; if ((i) == 0) st_ae[st_ae_cls * 4]++; } \
+    if ((i) == 5) st_ae_cls = -1; \
+    st_prev = st_now; }
+#define BL_STAMP_AFTER_END(ek) st_ae_cls = ((ek) & 16) ? 1 : (((ek) & 2) ? 0 : -1);
 // critical-control time split by what the tick decided: 0 next leaf of the subtree, 1 next doubling, 2 transition end / init
 #define BL_STAMP_KIND(k) st_kind = (k);
 #define BL_STAMP_CRIT { const long long st_now = (long long)clock64(); st_kn[st_kind]++; st_kc[st_kind] += st_now - st_prev; }
-#define BL_COUNT_SPINS(n) st_spins += (long long)(n);
+#define BL_COUNT_SPINS(n) { st_spins += (long long)(n); if (st_ae_cls >= 0) st_ae[st_ae_cls * 4 + 3] += (long long)(n); }
 // sub-steps of a decision: BL_SUB0 starts the clock, BL_SUB(i) charges the time since the last mark to slot i
 #define BL_SUB0 st_t = (long long)clock64();
 #define BL_SUB(i) { const long long st_n2 = (long long)clock64(); st_sub[i] += st_n2 - st_t; st_t = st_n2; }
@@ -64,6 +71,7 @@
 #define BL_STAMP_DECL
 #define BL_STAMP(i)
 #define BL_STAMP_KIND(k)
+#define BL_STAMP_AFTER_END(ek)
 #define BL_STAMP_CRIT
 #endif
 
@@ -91,9 +99,10 @@ struct BlNutsCold {
     int *status;                   // [1]
     int *xcd_local;                // [C] 1 if the chain ran on the L2-local exchange
     long long *dbg;                // [BL_DBG_SLOTS] phase cycle counters (diagnostic BL_STAMPS builds only); from 32: chain 0's site-evaluation
-                                   // cycles per compute wave, [workgroup][wave] at 8 per workgroup
+                                   // cycles per compute wave, [workgroup][wave] at 8 per workgroup; from 544: the tick behind a
+                                   // transition's end on chain 0's workgroups 0 and 1 (BL_STAMP_AFTER_END), 8 each
 };
-#define BL_DBG_SLOTS 544           // 32 + 64 workgroups x 8 compute waves
+#define BL_DBG_SLOTS 560           // 32 + 64 workgroups x 8 compute waves + 2 workgroups x 8
 
 struct BlNutsParams {
     const float *rows;             // HBM data matrix [n_rows][n_stride]
@@ -136,6 +145,9 @@ struct BlCtlScalars {
     long long nleap_w, nleap_s;
 };
 enum { SV_TH = 0, SV_GR, SV_ZL, SV_RL, SV_GL, SV_ZR, SV_RR, SV_GRR, SV_ZP, SV_GP, SV_RSUM, SV_WFMEAN, SV_WFM2, SV_MOMZ };
+// (the tree's slots are free since it moved to registers; four of them hold launch constants that would cost the loop registers:
+// the two halves of a lane's output address, the adaptation windows' ends by lane, and in lanes 0 / 1 the abort word's address)
+enum { SV_OUT_LO = SV_TH, SV_OUT_HI = SV_GR, SV_WINEND = SV_ZL, SV_ABORT = SV_RL };
 
 __device__ __forceinline__ float bl_exp(float x) { return __builtin_amdgcn_exp2f(x * BL_LOG2E); }
 __device__ __forceinline__ float bl_log(float x) { return BL_LN2 * __builtin_amdgcn_logf(x); }
@@ -248,6 +260,33 @@ struct BlSpinBound {
 __host__ __device__ __forceinline__ constexpr int bl_pair_pos(int v) { return v < 8 ? 2 * v : 2 * (v - 8) + 1; }
 __host__ __device__ __forceinline__ constexpr int bl_pair_lane(int v) { return v < 8 ? v : 24 + v; }
 typedef unsigned BlU4 __attribute__((ext_vector_type(4)));
+// The per-draw outputs of workgroup 0 (draws, num_steps, accept_prob, potential, diverging).  Their five pointers sit in the cold block,
+// which the kernel also writes, so read at the store they are three device-memory round trips one behind the other -- and flat stores,
+// which the next LDS wait observes too -- on the one workgroup the whole chain waits for.  1: every lane forms ITS output's address once,
+// in front of the loop (lane d < D: coordinate d of the chain's draws; lanes D ... D + 3: num_steps, accept_prob, potential, diverging --
+// D + 4 <= 64 as for the exchange's granules); a draw is then one address computation, one dword global store and one byte global
+// store with no device-memory load in front and no wait behind.  The address is kept in the control wave's LDS block, not in
+// registers: four more loop-carried VGPRs tipped 73 of the fuller instantiations (occu_rn's headline pair among them) into scratch,
+// and its read joins the LDS read-modify-write that a sampling transition's end makes anyway.  The adaptation windows' ends go the
+// same way: slot i keeps win_end[i].  0: through the cold block at every draw (A/B).
+#ifndef BL_OUT_DIRECT
+#define BL_OUT_DIRECT 1
+#endif
+// The host's abort request is a word of HOST memory: read in front of a publish (every 256th evaluation) it put a PCIe round trip, behind
+// a device round trip for its pointer, in front of the record that all of the chain's control waves poll for.  1: the first compute wave
+// of workgroup 0 issues the load BEHIND the publish of evaluation 256 n and leaves the value in a register; BL_ABORT_LAG evaluations
+// later -- the load's wait stands there, at the use -- it sets a sticky LDS word, and the evaluation after that carries the word in
+// granule D + 1.  The lag: a read over PCIe returns in 1 - 3 us on an idle link and can take several times that under traffic; the
+// shortest tick any form has is 1.6 us, so 8 evaluations are >= 13 us, and a request is seen 9 evaluations later than before in a
+// sampling period of 256.  0, the default: synchronous read in front of the publish.  Measured and not kept (profiles/NOTES.md,
+// profiles/output_path/): alone -0.6 % on the headline, together with BL_OUT_DIRECT 0.0 %, the secondary workloads +-1 - 2 %.
+#ifndef BL_ABORT_DEFER
+#define BL_ABORT_DEFER 0
+#endif
+#define BL_ABORT_LAG 8u
+typedef __attribute__((address_space(1))) unsigned BlGlobalU;
+typedef __attribute__((address_space(1))) unsigned char BlGlobalB;
+typedef __attribute__((address_space(1))) const int BlGlobalCI;
 #ifndef BL_GRP_FORM
 #define BL_GRP_FORM 2 // what the sampler's GRP instantiation carries: 2 = the lane-group evaluator alone, 1 = both evaluators (A/B)
 #endif
@@ -266,6 +305,13 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
     // which of the two paths a kernel has is a compile-time fact: the one-workgroup kernels carry no publish / poll, the others no
     // k == 1 branches (stacked 2.525 -> 2.513 us, dynamic 4.99 -> 4.95: profiles/r04/i_ab_split_single.txt)
     constexpr bool multi_wg = !(GRP && CW == BL_CWAVES_SINGLE);
+    // (the deferred abort sample costs the compute waves a loop-carried register: the lean kernels have it to spare, occu_rn's -- at
+    // the 256-register budget -- and the general forms that already spill keep the synchronous read)
+    constexpr bool ABORT_DEFER = BL_ABORT_DEFER && LEAN && MODEL != 1;
+    // (the per-draw outputs through addresses formed once: where it was measured to gain -- the one-pair-per-lane and Royle-Nichols
+    // kernels, the headline's among them; in the lane-group / one-workgroup instantiation the stacked workload LOST 2 % with it, cause
+    // not found, so that instantiation keeps the parent's code: profiles/NOTES.md, profiles/output_path/)
+    constexpr bool OUT_DIRECT = BL_OUT_DIRECT && !GRP;
     // XCD-aware mapping (speed only; see header): label = b % 8 names a set of blocks that share an XCD.
     // Wide geometry (slices that only fit LDS when a chain takes more than one XCD's CUs): consecutive blocks, any XCD.
     const int label = blockIdx.x & 7, slot = blockIdx.x >> 3;
@@ -307,6 +353,7 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
     int *sh_flag = bl_lds_i(BL_OFF_FLAG);
     float *sh_ckr = bl_lds_f(BL_OFF_CKR), *sh_ckrs = bl_lds_f(BL_OFF_CKRS);
     float *sv = bl_lds_f(BL_OFF_SV) + lane;  // state vector slot s of this lane: sv[s * 64]
+    unsigned *svu = reinterpret_cast<unsigned *>(sv); // (the slots that hold words, not floats: SV_OUT_LO ... SV_ABORT)
     BlCtlScalars *ss = reinterpret_cast<BlCtlScalars *>(bl_smem_raw + BL_OFF_SS);
     if (tid < 64) sh_coef[tid] = 0.0f;
     __syncthreads();
@@ -422,6 +469,22 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
 #pragma unroll
         for (int s = 0; s < 16; s++) sv[s * 64] = 0.0f;
         sv[SV_MOMZ * 64] = z_first;
+        if constexpr (OUT_DIRECT) { // this lane's output address at draw 0 of its chain, and the window ends by lane
+            const size_t cs = (size_t)chain * S;
+            unsigned char *ob = nullptr;
+            if (lane < D) ob = reinterpret_cast<unsigned char *>(cold->draws + cs * D + lane);
+            else if (lane == D) ob = reinterpret_cast<unsigned char *>(cold->num_steps + cs);
+            else if (lane == D + 1) ob = reinterpret_cast<unsigned char *>(cold->accept_prob + cs);
+            else if (lane == D + 2) ob = reinterpret_cast<unsigned char *>(cold->potential + cs);
+            else if (lane == D + 3) ob = cold->diverging + cs;
+            svu[SV_OUT_LO * 64] = (unsigned)(size_t)ob;
+            svu[SV_OUT_HI * 64] = (unsigned)((size_t)ob >> 32);
+            svu[SV_WINEND * 64] = (unsigned)cold->win_end[lane & 31];
+        }
+        if constexpr (ABORT_DEFER) { // (lanes 0 and 1: the halves of the abort word's address, for the compute wave that samples it)
+            const size_t ab = (size_t)cold->abort_flag;
+            if (lane < 2) svu[SV_ABORT * 64] = (unsigned)(ab >> (32 * lane));
+        }
         if (lane == 0) {
             sh_flag[0] = 0; sh_flag[1] = 0; sh_flag[2] = 0; // run status; L2-local exchange proven; (spare)
             for (int w = 0; w < 16; w++) bl_lds_i(BL_OFF_TAG)[w] = 0; // no row of the partial table belongs to an evaluation yet
@@ -470,11 +533,26 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
             if (end_kind & 8) {
                 const int wi = ss->win_idx + 1;
                 ss->win_idx = wi;
-                win_end_cur = cold->win_end[wi < 31 ? wi : 31]; // (beside the next transition's first evaluation)
+                if constexpr (OUT_DIRECT) win_end_cur = (int)(svu - lane)[SV_WINEND * 64 + (wi < 31 ? wi : 31)];
+                else win_end_cur = cold->win_end[wi < 31 ? wi : 31]; // (beside the next transition's first evaluation)
             }
         } else if (end_kind & 16) {
             ss->nleap_s += nprop;
-            if (member == 0) {
+            if (OUT_DIRECT && member == 0) {
+                // one dword per lane <= D + 2 and lane D + 3's byte, through the addresses formed in front of the loop (read back with
+                // the LDS traffic this branch has anyway)
+                // (which output a lane has is worked out HERE, from an opaque copy of the lane id: as loop invariants the five lane masks
+                // took ten SGPRs across the loop, and the headline kernel, at 104, spilled five)
+                int lane_o = lane;
+                asm volatile("" : "+v"(lane_o));
+                const int r = lane_o - D;
+                const float accp = t_sumacc * bl_rcp((float)nprop);
+                const unsigned val = r < 0 ? __float_as_uint(th) : (r == 0 ? (unsigned)nprop : __float_as_uint(r == 1 ? accp : (float)U));
+                const unsigned stride = r < 0 ? 4u * (unsigned)D : (r == 3 ? 1u : 4u);
+                unsigned char *dst = reinterpret_cast<unsigned char *>(((size_t)svu[SV_OUT_HI * 64] << 32) | svu[SV_OUT_LO * 64]) + (size_t)(unsigned)(it - W) * stride;
+                if (r <= 2) *(BlGlobalU *)dst = val;
+                else if (r == 3) *(BlGlobalB *)dst = pend_sdiv ? 1 : 0;
+            } else if (member == 0) {
                 const size_t s = (size_t)chain * S + (it - W);
                 if (act) cold->draws[s * D + lane] = th;
                 if (lane == 0) {
@@ -739,6 +817,8 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
         bool rvalid = false;
         float rvmask = 0.0f;
         if constexpr (RESIDENT) bl_load_resident_rec(tid - 64, ld, cnt, rrec, rvalid, rvmask);
+        int ab_raw = 0; // (BL_ABORT_DEFER: the abort word's sample in flight)
+        const unsigned ab_mask = (__builtin_amdgcn_readfirstlane(wave) == 1 && member == 0) ? 0u : 0x80000000u;
         while (true) {
             // The loop control of this tick (run status, "the exchange is L2-local") is read in ONE ds_read_b64 that is issued here
             // and looked at after the evaluation: read and tested first -- two dependent LDS round trips, as it was until round 3 --
@@ -792,8 +872,13 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
                     for (int w = 0; w < CW; w++) comp += part_all ? (float)part[w * part_rs + sp * BL_SP_PART(KS, KO)] : 0.0f;
                 }
                 if (lane > D) comp = 0.0f;
-                if (lane == D + 1 && member == 0 && (epoch_c & 255u) == 0u)
-                    comp = (__hip_atomic_load(cold->abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) ? 1.0f : 0.0f;
+                if constexpr (ABORT_DEFER) { // the word that the sampling wave set behind the last evaluation's publish (below)
+                    if (lane == D + 1 && member == 0 && (epoch_c & 255u) == BL_ABORT_LAG + 1u)
+                        comp = (*(__attribute__((address_space(3))) const volatile int *)(sh_flag + 2) != 0) ? 1.0f : 0.0f;
+                } else {
+                    if (lane == D + 1 && member == 0 && (epoch_c & 255u) == 0u)
+                        comp = (__hip_atomic_load(cold->abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) ? 1.0f : 0.0f;
+                }
                 if (epoch_c == 1u) { // placement census: all k XCC ids equal  <=>  k * sum(x^2) == (sum x)^2
                     const float xcc = (float)bl_xcc_id(); // (read here, once: as a loop-carried value it was spilled to scratch and reloaded on every publish)
                     if (lane == D + 2) comp = xcc;
@@ -819,6 +904,24 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
             // (Measured and dropped: no barrier here -- the control wave polling straight after its decisions, a counter of coefficient
             // reads guarding the one write that the barrier ordered: 2 % slower, the poll loop competes with the evaluation's tail.)
             __syncthreads(); // (the control wave's decisions are done)
+            if constexpr (ABORT_DEFER) {
+                // The host's abort request, sampled BEHIND the publish and consumed BL_ABORT_LAG evaluations later (see BL_ABORT_DEFER):
+                // the value stays in a register meanwhile, so the load's wait stands at the second branch.  BETWEEN the two barriers:
+                // there the compute waves only wait for the control wave's gather and position.  (In front of the first barrier --
+                // one exec-masked test per wave and tick on the evaluation's own path -- the stacked workload ran 0.7 % and the
+                // one-workgroup form 1.0 % slower than the parent, beyond the bar: profiles/output_path/ab_first_placement.txt.)
+                // One scalar test per tick: ab_mask is 0 in the sampling wave and has the top bit set in every other.
+                const unsigned ph = (epoch_c & 255u) | ab_mask;
+                if (__builtin_expect(ph <= BL_ABORT_LAG, 0)) {
+                    if (ph == 0u) {
+                        const unsigned *abw = reinterpret_cast<const unsigned *>(bl_lds_f(BL_OFF_SV)) + SV_ABORT * 64;
+                        BlGlobalCI *ab_ptr = (BlGlobalCI *)(((size_t)abw[1] << 32) | abw[0]);
+                        if (lane == 0) ab_raw = __hip_atomic_load(ab_ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    } else if (ph == BL_ABORT_LAG) {
+                        if (lane == 0 && ab_raw != 0) sh_flag[2] = 1; // (sticky; read by the publisher / the one-workgroup control wave one evaluation on)
+                    }
+                }
+            }
             __syncthreads(); // the next position is in LDS
         }
     } else {
@@ -838,10 +941,12 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
             BL_STAMP_CRIT
             BL_STAMP(0)
         } else if (!SPEC) {
+            BL_STAMP_AFTER_END(end_kind)
             end_deferred();
             run_deferred(); // non-speculative form (HYBRID: a tick whose decisions came first): only the bookkeeping overlaps the evaluation
             BL_STAMP(0)
         } else {
+            BL_STAMP_AFTER_END(end_kind)
             end_deferred(); // beside the evaluation of the new transition's first leaf
             BL_STAMP(0)
         }
@@ -936,8 +1041,14 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
                     for (int w = 0; w < CW; w++) comp += part_all ? part[w * part_rs + sp * BL_SP_PART(KS, KO)] : 0.0f;
                 }
                 if (lane > D) comp = 0.0f;
-                if (lane == D + 1 && (epoch & 255u) == 0u) // the host's abort request (fit(timeout=...))
-                    comp = (__hip_atomic_load(cold->abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) ? 1.0f : 0.0f;
+                // the host's abort request (fit(timeout=...)): sampled by the first compute wave, see BL_ABORT_DEFER
+                if constexpr (ABORT_DEFER) {
+                    if (lane == D + 1 && (epoch & 255u) == BL_ABORT_LAG + 1u)
+                        comp = (*(__attribute__((address_space(3))) const volatile int *)(sh_flag + 2) != 0) ? 1.0f : 0.0f;
+                } else {
+                    if (lane == D + 1 && (epoch & 255u) == 0u)
+                        comp = (__hip_atomic_load(cold->abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) ? 1.0f : 0.0f;
+                }
                 acc = (double)comp;
             } else if (PAIRS) {
                 // paired records: four 16-byte sc1 loads per lane and round (see BL_POLL_PAIRS); loads beyond ceil(nq / 2) would only
@@ -1120,6 +1231,8 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
         cold->dbg[14] = st_kc[0]; cold->dbg[15] = st_kc[1]; cold->dbg[7] = st_kc[2];
         for (int i = 0; i < 4; i++) cold->dbg[16 + i] = st_sub[i];
     }
+    if (cold->dbg && chain == 0 && member < 2 && tid == 0) // the tick behind a transition's end, on workgroup 0 and on one other
+        for (int i = 0; i < 8; i++) cold->dbg[544 + member * 8 + i] = st_ae[i];
     if (cold->dbg && chain == 0 && member < 32 && wave >= 1 && wave <= 8 && (tid & 63) == 0) {
         cold->dbg[32 + member * 8 + (wave - 1)] = st_sub[5];
         unsigned hw; // where the hardware put this wave: HW_ID bits 5:4 = SIMD, 11:8 = CU, 3:0 = wave slot

@@ -330,7 +330,7 @@ int bl_host_free(void *ptr);
 
 /* In-kernel phase cycle counters of the last launch; all zero unless the library is a diagnostic
  * BL_STAMPS build (make -C biolith_amd/csrc stamps).  Not part of the reference's interface. */
-int bl_nuts_debug_counters(bl_dataset *ds, int64_t *out /*[n<=544]*/, int n);
+int bl_nuts_debug_counters(bl_dataset *ds, int64_t *out /*[n<=560]*/, int n);
 
 /*
  * Deterministic sites (occu.py:207, 221-228), recomputed from draws on the device:

@@ -26,7 +26,8 @@ def main():
     for k in ks:
         for chains in (4,):
             r = ds.nuts(num_warmup=1000, num_samples=1000, num_chains=chains, seed=0, wgs_per_chain=k)
-            c = ds.debug_counters()
+            call = ds.debug_counters(560)
+            c = call[:32]
             ticks, rt = int(c[8]), int(c[9])
             tot = c[:7].sum()
             mhz = tot / (rt / 100.0) if rt else float("nan")  # s_memrealtime ticks at 100 MHz
@@ -44,6 +45,14 @@ def main():
                   % (c[16] / n_end, c[17] / n_end, c[18] / n_end))
             for name, n_, cyc in zip(("next leaf of the subtree", "next doubling", "transition end / init"), kn, kc):
                 print(f"    decisions, {name:26s}: {int(n_):7d} ticks ({100 * n_ / max(ticks, 1):4.1f} %), {cyc / max(n_, 1):7.0f} cyc each")
+            # The tick BEHIND a transition's end (its stamp 0 is end_deferred alone), on workgroup 0 -- which alone writes a draw's
+            # outputs -- and on workgroup 1, for warm-up and sampling transitions apart (the kernel sorts them: no subtraction)
+            for wg in (0, 1):
+                a = call[544 + 8 * wg: 552 + 8 * wg].astype(float)
+                for label, (n_, s0, s1, sp) in (("warm-up", a[:4]), ("sampling", a[4:])):
+                    n1 = max(n_, 1.0)
+                    print(f"    tick behind a transition's end, workgroup {wg}, {label:8s}: {int(n_):6d} ticks, stamp 0 (end_deferred) {s0 / n1:6.0f} cyc | "
+                          f"wait for the compute waves {s1 / n1:6.0f} cyc | poll rounds {sp / n1 + 1:.2f}")
             # the same counters of a launch that is warm-up only (1000 + 2), subtracted -> the sampling phase alone:
             # the adaptation's share of a transition's end (dual averaging, Welford moments, window ends) must be gone there
             rw = ds.nuts(num_warmup=1000, num_samples=2, num_chains=chains, seed=0, wgs_per_chain=k)
