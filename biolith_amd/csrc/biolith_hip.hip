@@ -32,6 +32,7 @@
 #include "predictive_density.hpp"
 #include "psis_loo.hpp"
 #include "site_summary.hpp"
+#include "site_diagnostics.hpp"
 #include "regional_totals.hpp"
 
 // ------------------------------------------------------------------ errors ----
@@ -2476,6 +2477,64 @@ extern "C" int bl_site_summary(bl_dataset *ds, int n_draws, const float *draws, 
         if (s.sd) BL_HIP(hipMemcpy(s.sd, s.d_sd, s.cells * 8, hipMemcpyDeviceToHost));
         if (s.order) BL_HIP(hipMemcpy(s.order, s.d_order, s.cells * 4 * p.n_ranks, hipMemcpyDeviceToHost));
     }
+    return BL_OK;
+}
+
+// ---- the deterministic sites' convergence diagnostics over the chains' draws: n_eff, split r_hat, mean and sd per cell, fused ----
+// (No counterpart in the reference.)  Kernels: site_diagnostics.hip.  As bl_site_summary: a launch per wanted site over all the draws,
+// which goes out when they are up and is done before run_over_draws lets go of them.
+extern "C" int bl_site_diagnostics(bl_dataset *ds, int n_draws, const float *draws, int n_chains, double *psi_n_eff, double *psi_r_hat,
+                                   double *psi_mean, double *psi_sd, double *prob_n_eff, double *prob_r_hat, double *prob_mean,
+                                   double *prob_sd)
+{
+    const bool first = psi_n_eff || psi_r_hat || psi_mean || psi_sd, second = prob_n_eff || prob_r_hat || prob_mean || prob_sd;
+    if (!ds || !draws || n_draws <= 0 || !(first || second)) return bl_fail(BL_ERR_INVALID, "bl_site_diagnostics: bad argument");
+    if (ds->nsp > 1) return bl_fail(BL_ERR_UNSUPPORTED, "bl_site_diagnostics: a joint-species handle samples; take the sites from one handle per species");
+    if (ds->model == 8) return bl_fail(BL_ERR_UNSUPPORTED, "bl_site_diagnostics: the dynamic occupancy model's sites (psi, gamma, eps) are formed by the caller from the draws");
+    if (ds->model == 6 && ds->re.kind == 8)
+        return bl_fail(BL_ERR_UNSUPPORTED, "bl_site_diagnostics: occu_comb's sites (psi, PC / ARU detection probabilities) are formed by the caller from the draws");
+    if (ds->in_flight) return bl_fail(BL_ERR_BUSY, "a NUTS launch is in flight on this handle");
+    if (n_chains < 1 || n_draws % n_chains != 0)
+        return bl_fail(BL_ERR_INVALID, "bl_site_diagnostics: n_draws=%d is not n_chains=%d chains of equal length", n_draws, n_chains);
+    if (n_draws / n_chains < 2)
+        return bl_fail(BL_ERR_INVALID, "bl_site_diagnostics: %d draws per chain, at least 2", n_draws / n_chains);
+    int rc = set_device(ds);
+    if (rc || (second && (rc = upload_once(&ds->d_wraw, ds->h_wraw)))) return rc;
+    BlSiteDiagnosticsParams p{};
+    p.rows = ds->d_rows; p.wraw = ds->d_wraw; p.ns = ds->n_stride;
+    p.N = ds->dims.n_sites; p.T = ds->dims.n_periods; p.J = ds->dims.n_replicates; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = ds->D;
+    p.model = branch_model(ds); p.c = draw_coords(ds); p.n_chains = n_chains; p.n = n_draws / n_chains;
+    const size_t sites = (size_t)p.N, visits = sites * p.T * p.J;
+    // one site's host arrays and the device outputs they come back from: n_eff, r_hat, mean, sd
+    struct Site {
+        size_t cells;
+        double *host[4];
+        double *dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    } site[2] = {{sites, {psi_n_eff, psi_r_hat, psi_mean, psi_sd}}, {visits, {prob_n_eff, prob_r_hat, prob_mean, prob_sd}}};
+    DevScratch scratch;
+    for (Site &s : site)
+        for (int k = 0; k < 4; k++)
+            if (s.host[k]) BL_HIP(scratch.alloc((void **)&s.dev[k], s.cells * 8));
+    // the chains' means: one workspace, sized for the larger of the launches (they run one after the other)
+    const size_t ws = std::max(first ? bl_site_diagnostics_workspace(&p, false) : 0, second ? bl_site_diagnostics_workspace(&p, true) : 0);
+    BL_HIP(scratch.alloc((void **)&p.means, ws * 8));
+    void *none = nullptr;
+    const DrawOut outs[] = {{nullptr, 0, &none, false}}; // (nothing per draw)
+    rc = run_over_draws(ds, n_draws, draws, 0, outs, [&](const float *d_draws, int n0, int, int) {
+        if (n0 != 0) return hipSuccess;
+        p.draws = d_draws;
+        int e = 0;
+        for (int k = 0; k < 2 && !e; k++) {
+            p.n_eff = site[k].dev[0]; p.r_hat = site[k].dev[1]; p.mean = site[k].dev[2]; p.sd = site[k].dev[3];
+            if (p.n_eff || p.r_hat || p.mean || p.sd) e = k ? bl_launch_site_diagnostics_prob(&p, nullptr) : bl_launch_site_diagnostics_psi(&p, nullptr);
+        }
+        if (!e) e = (int)hipStreamSynchronize(nullptr);
+        return (hipError_t)e;
+    });
+    if (rc) return rc;
+    for (const Site &s : site)
+        for (int k = 0; k < 4; k++)
+            if (s.host[k]) BL_HIP(hipMemcpy(s.host[k], s.dev[k], s.cells * 8, hipMemcpyDeviceToHost));
     return BL_OK;
 }
 

@@ -495,6 +495,28 @@ class OccuDataset:
         _ffi.check(self._lib.bl_site_summary(self._h, n, _fp(d), int(r.size), r32.ctypes.data_as(C.POINTER(C.c_int32)), *ptrs))
         return tuple(out)
 
+    def site_diagnostics(self, draws, n_chains: int, psi: bool = True, prob_detection: bool = True):
+        """The deterministic sites' convergence diagnostics over draws (C n, D) of ``n_chains`` = C chains, chain-major, fused on the
+        device (BUILDER-DEFINED): ``psi_n_eff, psi_r_hat, psi_mean, psi_sd, prob_n_eff, prob_r_hat, prob_mean, prob_sd``, float64.  The
+        first site (``psi``; occu_rn, nmixture: ``abundance``) is constant over the periods and comes back per site, (N,); the second
+        (``prob_detection``; occu_cop: ``rate_detection``) (J, T, N).  ``n_eff`` and ``r_hat`` are numpyro's effective sample size and
+        split R-hat of the cell's float32 values of ``deterministic``, by direct lagged sums in float64 (include/biolith_hip.h:
+        bl_site_diagnostics); ``mean`` and ``sd`` are ``site_summary``'s.  ``None`` for a site that is not wanted.  Nothing of size
+        (C n, T, N) or (C n, J, T, N) exists on the device or the host.  Draws must be finite."""
+        d = self._draw_matrix(draws)
+        total, C_ = d.shape[0], int(n_chains)
+        if not (psi or prob_detection):
+            raise ValueError("site_diagnostics(): neither site is wanted")
+        if C_ < 1 or total == 0 or total % C_:
+            raise ValueError(f"site_diagnostics(): {total} draws are not {C_} chains of equal length")
+        if total // C_ < 2:
+            raise ValueError(f"site_diagnostics(): {total // C_} draws per chain, at least 2")
+        out = []
+        for want, shape in ((psi, (self.N,)), (prob_detection, (self.J, self.T, self.N))):
+            out += [np.empty(shape) if want else None for _ in range(4)]
+        _ffi.check(self._lib.bl_site_diagnostics(self._h, total, _fp(d), C_, *[_dp(a) for a in out]))
+        return tuple(out)
+
     def regional_totals(self, draws, region, n_regions: int, weight=None, seed: int = 0, site: bool = True, latent: bool = True):
         """Per draw of draws (n, D) and region, the weighted totals of the first deterministic site and of the latent state, fused on
         the device (BUILDER-DEFINED): ``site_total`` (n, n_regions) and ``latent_total`` (n, T, n_regions), float64, ``None`` where not

@@ -364,6 +364,35 @@ int bl_site_summary(bl_dataset *ds, int n_draws, const float *draws, int n_ranks
                     float *psi_order, double *prob_mean, double *prob_sd, float *prob_order);
 
 /*
+ * The convergence diagnostics of the deterministic sites, fused -- BUILDER-DEFINED (the reference's users run
+ * numpyro.diagnostics.summary over predict()'s arrays on the host): per cell of bl_deterministic's two sites, the effective sample size
+ * and the split R-hat over the draws of n_chains chains, without the arrays [n_draws][T][N] and [n_draws][J][T][N] ever being stored.
+ * draws is chain-major: with n = n_draws / n_chains, chain c owns draws c n .. c n + n - 1.  With x[c][t] the cell's float32 value of
+ * bl_deterministic under draw c n + t, bit for bit, widened to float64, and C = n_chains -- numpyro's estimator:
+ *   m_c     = (sum_t x[c][t]) / n;   s2_c = sum_t (x[c][t] - m_c)^2 / (n - 1)
+ *   W       = (sum_c s2_c) / C;   plus = W (n - 1) / n;   C > 1: plus += sum_c (m_c - mean_c m_c)^2 / (C - 1);   C == 1: W = plus
+ *   gamma_k = (sum_c sum_{t < n - k} (x[c][t] - m_c)(x[c][t + k] - m_c)) / C / n
+ *   rho_k   = 1 - (W - gamma_k) / plus,  rho_0 = 1;   P_p = rho_{2p} + rho_{2p+1} for p < n / 2 (an odd last lag is dropped)
+ *   tau     = -1 + 2 (P_0 + sum_{p >= 1} min_{1 <= q <= p} max(P_q, 0));   n_eff = C n / tau
+ *   r_hat   = sqrt(plus' / W'), plus' and W' as above over the 2 C half chains x[c][0 .. h - 1] and x[c][n - h .. n - 1], h = n / 2
+ *   mean, sd: bl_site_summary's, over all C n draws in draw order
+ * P_0 is not clipped; for very short chains tau, and with it n_eff, may be negative.  A cell whose values are all equal has 0 / 0 in
+ * rho and in r_hat: NaN for both; r_hat is NaN where a half holds one draw (n < 4).  Every sum runs in float64 in draw order, chain after
+ * chain; the lagged sums are formed directly, a block of lags a pass over the chains.  Once a clipped pair is 0 every later term of tau
+ * is +0, so a cell stops there, exactly; how many passes its neighbours take changes nothing.  No atomics: a cell's outputs are a
+ * function of its covariates, its effects and the draws alone -- not of N, of the other outputs asked for or of the launch --, and two
+ * calls return the same bits.
+ * The first site (psi; occu_rn, nmixture: abundance) is constant over the periods and comes back per site, [N]; the second
+ * (prob_detection; occu_cop: rate_detection) [J][T][N].  float64 on the host, NULL = skip (all eight NULL: BL_ERR_INVALID); the kernel
+ * of a site none of whose outputs is wanted is not launched.  n_chains < 1, n_draws not divisible by n_chains, or fewer than 2 draws per
+ * chain: BL_ERR_INVALID.  Draws must be finite.  Device workspace: three float64 per chain and cell; nothing grows with n.  Serves what
+ * bl_site_summary serves, with its refusals (BL_ERR_UNSUPPORTED: a joint-species handle, occu_dyn, occu_comb; BL_ERR_BUSY while a NUTS
+ * launch is in flight on the handle).
+ */
+int bl_site_diagnostics(bl_dataset *ds, int n_draws, const float *draws, int n_chains, double *psi_n_eff, double *psi_r_hat,
+                        double *psi_mean, double *psi_sd, double *prob_n_eff, double *prob_r_hat, double *prob_mean, double *prob_sd);
+
+/*
  * The posterior of totals over sets of sites, fused -- BUILDER-DEFINED (the reference's users form predict()'s arrays and sum them on
  * the host): per posterior draw and region, the weighted total of the first deterministic site and of the latent state, without the
  * arrays [n_draws][T][N] ever being stored.  region[i] in 0 .. n_regions - 1 is site i's region, -1 = in no region; weight[i] is finite
