@@ -34,6 +34,7 @@
 #include "site_summary.hpp"
 #include "site_diagnostics.hpp"
 #include "regional_totals.hpp"
+#include "response_curves.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -2599,6 +2600,54 @@ extern "C" int bl_regional_totals(bl_dataset *ds, int n_draws, const float *draw
                             {latent_total, (size_t)T * G * 8, (void **)&p.latent_total, false},
                             {nullptr, rows * W * 8, (void **)&p.part, true}};
     return run_over_draws(ds, n_draws, draws, rows * std::max(W, G) * 8, outs, p, bl_launch_regional_totals);
+}
+
+// ---- response curves: per draw and grid value the weighted total over the sites with one covariate set to the value, fused ----
+// (No counterpart in the reference.)  Kernels: response_curves.hip.  The site side reads the site covariates at the head of the handle's
+// rows, the obs side the raw observation covariates (up on first use); next to them go up the grid values and the weights, nothing
+// else.  run_over_draws cuts the draws so that the workspace, n_values rows of one double per run of 64 sites a draw, stays within
+// BL_TOTALS_WORKSPACE_BYTES.
+extern "C" int bl_response_curves(bl_dataset *ds, int n_draws, const float *draws, int side, int covariate, int n_values,
+                                  const float *values, const double *weight, double *curve_total)
+{
+    int rc = per_draw_front("bl_response_curves", ds, n_draws, draws, true,
+                            [](const bl_dataset *d) {
+                                return d->nsp == 1 && ((d->model >= 0 && d->model <= 4) || re_kind_in(d, {0, 1, 2, 3, 4, 5, 6, 7}));
+                            },
+                            "occu, occu_cs, occu_cop, occu_rn and nmixture: the handles of bl_regional_totals");
+    if (rc) return rc;
+    const int N = ds->dims.n_sites, V = n_values;
+    if (side != 0 && side != 1) return bl_fail(BL_ERR_INVALID, "bl_response_curves: side=%d, 0 (site) or 1 (obs)", side);
+    const int K = side ? ds->Ko : ds->Ks;
+    if (covariate < 0 || covariate >= K)
+        return bl_fail(BL_ERR_INVALID, "bl_response_curves: covariate=%d outside 0 .. %s - 1 = %d", covariate, side ? "Ko" : "Ks", K - 1);
+    if (V < 1) return bl_fail(BL_ERR_INVALID, "bl_response_curves: n_values=%d, at least 1", V);
+    if (!values) return bl_fail(BL_ERR_INVALID, "bl_response_curves: values is NULL");
+    if (!curve_total) return bl_fail(BL_ERR_INVALID, "bl_response_curves: curve_total is NULL");
+    for (int g = 0; g < V; g++)
+        if (!std::isfinite(values[g])) return bl_fail(BL_ERR_INVALID, "bl_response_curves: values[%d]=%g is not finite", g, (double)values[g]);
+    for (int i = 0; weight && i < N; i++)
+        if (!std::isfinite(weight[i])) return bl_fail(BL_ERR_INVALID, "bl_response_curves: weight[%d]=%g is not finite", i, weight[i]);
+    if (side && (rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
+
+    BlResponseCurvesParams p{};
+    p.rows = ds->d_rows; p.wraw = ds->d_wraw; p.ns = ds->n_stride;
+    p.N = N; p.T = ds->dims.n_periods; p.J = ds->dims.n_replicates; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = ds->D;
+    p.model = branch_model(ds); p.c = draw_coords(ds);
+    p.side = side; p.k = covariate; p.n_values = V; p.n_runs = (N + 63) / 64;
+    DevScratch scratch;
+    float *d_values = nullptr;
+    double *d_w = nullptr;
+    BL_HIP(scratch.alloc((void **)&d_values, (size_t)V * 4));
+    BL_HIP(hipMemcpy(d_values, values, (size_t)V * 4, hipMemcpyHostToDevice));
+    if (weight) {
+        BL_HIP(scratch.alloc((void **)&d_w, (size_t)N * 8));
+        BL_HIP(hipMemcpy(d_w, weight, (size_t)N * 8, hipMemcpyHostToDevice));
+    }
+    p.values = d_values; p.weight = d_w;
+    const size_t per_draw = (size_t)V * p.n_runs * 8; // the workspace's bytes a draw (>= the totals')
+    const DrawOut outs[] = {{curve_total, (size_t)V * 8, (void **)&p.total, false}, {nullptr, per_draw, (void **)&p.part, true}};
+    return run_over_draws(ds, n_draws, draws, per_draw, outs, p, bl_launch_response_curves);
 }
 
 // ------------------------------------------------------- multi-GPU: the gather of the draws over RCCL ----

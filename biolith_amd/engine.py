@@ -541,6 +541,26 @@ class OccuDataset:
                                                 r.ctypes.data_as(C.POINTER(C.c_int32)), _dp(w), _dp(out_site), _dp(out_latent)))
         return out_site, out_latent
 
+    def response_curves(self, draws, side: int, covariate: int, values, weight=None):
+        """Per draw of draws (n, D) and grid value, the weighted total over the sites of a deterministic site with one covariate set to
+        the value at every site, fused on the device (BUILDER-DEFINED): (n, V) float64.  ``side`` 0 replaces site covariate
+        ``covariate`` and totals the first site (``psi``; occu_rn, nmixture: ``abundance``); ``side`` 1 replaces observation covariate
+        ``covariate`` at every visit and totals the second (``prob_detection``; occu_cop: ``rate_detection``) summed over a site's
+        T J visits.  ``values`` (V,) finite float32; ``weight`` (N,) finite float64, ``None`` = 1.  The terms are ``deterministic``'s
+        float32 values on the modified covariates, bit for bit, times the weight in float64, summed in ``regional_totals``' order for
+        one region (include/biolith_hip.h: bl_response_curves).  Nothing of size (n, V, N) exists on the device or the host."""
+        d = self._draw_matrix(draws)
+        n = d.shape[0]
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.float32).reshape(-1))
+        w = None if weight is None else np.ascontiguousarray(np.asarray(weight, dtype=np.float64).reshape(-1))
+        if n == 0:
+            raise ValueError("response_curves(): no draws")
+        if w is not None and w.size != self.N:
+            raise ValueError(f"response_curves(): weight holds one entry per site ({self.N})")
+        out = np.empty((n, v.size))
+        _ffi.check(self._lib.bl_response_curves(self._h, n, _fp(d), int(side), int(covariate), int(v.size), _fp(v), _dp(w), _dp(out)))
+        return out
+
     def _per_draw(self, fn, draws, seed, outs, pinned=True):
         """Calls a per-draw entry ``fn(handle, n, draws, seed, *outputs)`` for draws (n, D).  ``outs`` lists (wanted, shape behind
         the draw axis, dtype) per output; returns the arrays, ``None`` where not wanted.  With ``pinned`` the 4-byte outputs come from

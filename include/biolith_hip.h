@@ -423,6 +423,42 @@ int bl_regional_totals(bl_dataset *ds, int n_draws, const float *draws, uint64_t
                        const double *weight, double *site_total, double *latent_total);
 
 /*
+ * The posterior of a covariate's average response curve (partial dependence, marginal standardisation), fused -- BUILDER-DEFINED (the
+ * reference's users copy the data once per grid value, form predict()'s arrays and average them on the host): per posterior draw and
+ * grid value, the weighted total over the sites of a deterministic site with ONE covariate set to the grid value at every site -- every
+ * other covariate and every effect left as the site has it --, without an array [n_draws][n_values][N] ever being stored.  side 0
+ * replaces site covariate `covariate` in 0 .. Ks - 1, side 1 observation covariate `covariate` in 0 .. Ko - 1 at every visit; the
+ * replacement applies at every site, one whose own value was NaN included.  values holds n_values finite float32; weight[i] is finite
+ * and may be zero or negative, NULL = 1.
+ *   side 0:  v_i^(g)(n) = the float32 bl_deterministic gives for the first site (psi; occu_rn, nmixture: abundance) on the handle whose
+ *            site covariate `covariate` is values[g] at every site, bit for bit
+ *              curve_total[n][g] = sum_i weight_i * (double) v_i^(g)(n)
+ *   side 1:  u_{v,i}^(g)(n) = the float32 bl_deterministic gives for the second site (prob_detection; occu_cop: rate_detection) at visit
+ *            v = t J + j on the handle whose observation covariate `covariate` is values[g] at every visit, bit for bit
+ *              s_i = sum_{v = 0 .. T J - 1} (double) u_{v,i}^(g)(n), float64 in ascending v, from the first term on
+ *              curve_total[n][g] = sum_i weight_i * s_i
+ *            Every cell counts, as bl_deterministic returns every cell.
+ * curve_total is [n_draws][n_values] float64 on the host.
+ * Order.  bl_regional_totals' for a single region: every product is formed in float64 and the sums run in float64 in one fixed order, no
+ * atomics: the sites in site order are cut into runs of 64, the last run filled up with -0.0 (a single site returns its term's bits); a
+ * run is summed as the tree (x_l + x_{l+32}), then lanes 16, 8, 4, 2, 1 apart, and the runs' sums are added in run order.  So side 0's
+ * column g is, byte for byte, bl_regional_totals' site_total for one region on the modified handle.  Column g is a function of the
+ * sites, the weights, the draws and values[g] alone: it is the same bytes whatever the other values and their number are, however the
+ * draws are chunked, and two calls return the same bytes.
+ * Workspace.  The device holds one double per (draw of a chunk, value, run of 64); the draws go through in chunks such that it is at
+ * most BL_TOTALS_WORKSPACE_BYTES -- or one draw's rows, should they alone be larger --, whatever n_draws is.  Next to it: the draws, the
+ * values and the weights.
+ * Refused with BL_ERR_INVALID, the message holding the offending value: side not 0 or 1; covariate outside 0 .. Ks - 1 (side 1:
+ * 0 .. Ko - 1), which is every covariate on a side without covariates; n_values < 1; a non-finite value or weight; values or
+ * curve_total NULL.  curve_total is untouched on any refusal.  Serves what bl_regional_totals serves -- occu, occu_cs, occu_cop, occu_rn,
+ * nmixture, with or without a false-positive rate / random effects --; occu_comb, occu_dyn and a joint-species handle:
+ * BL_ERR_UNSUPPORTED, the message names the model.  BL_ERR_BUSY while a NUTS launch is in flight on the handle.
+ */
+int bl_response_curves(bl_dataset *ds, int n_draws, const float *draws, int side /* 0 site, 1 obs */, int covariate,
+                       int n_values, const float *values, const double *weight /* [N], NULL = 1 */,
+                       double *curve_total /* [n_draws][n_values] */);
+
+/*
  * Posterior predictive draws of the discrete sites, one per posterior draw -- what
  * numpyro.infer.Predictive(model_fn, posterior_samples)(key, site_covs, obs_covs) samples in
  * biolith/utils/predict.py:66-92 (obs withheld, so no observation is masked):
