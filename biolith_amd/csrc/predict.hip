@@ -104,7 +104,7 @@ __global__ void bl_predict_scores_kernel(const BlPredictParams p)
             if (latent) latent[((size_t)(n - p.n0) * T + t) * N + i] = (unsigned char)zn;
             for (int j = 0; j < J; j++) {
                 const float nu = pm_visit_linear(p.wraw, ns, al, Ko, t * J + j, i);
-                const int fn = rng.uniform() < (float)zn / (1.0f + __expf(-nu)) ? 1 : 0;
+                const int fn = rng.uniform() < (float)zn * pm_sigmoid(nu) ? 1 : 0; // (z p_j, as bl_predict_kernel states it)
                 const float g = pm_normal(rng); // one normal per replicate
                 const size_t o = (((size_t)(n - p.n0) * J + j) * T + t) * N + i;
                 if (f_out) f_out[o] = (unsigned char)fn;

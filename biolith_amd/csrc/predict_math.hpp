@@ -11,7 +11,10 @@
 
 namespace {
 
-__device__ __forceinline__ float pm_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
+// The reciprocal is the instruction itself, not `1.0f / d`: the build lets a float32 division be either that instruction or the correctly
+// rounded sequence, and the compiler chose per call site (bl_predict_kernel's psi got the sequence, bl_psi_kernel's the instruction), so
+// the threshold z is drawn against differed from the psi `deterministic` returns in the last bit of some cells.
+__device__ __forceinline__ float pm_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
 // b . (1, x), the intercept first; covariate k at x[k * stride] (1: staged in registers; n_stride: read from the rows at one site)
 __device__ __forceinline__ float pm_linear(const float *__restrict__ x, size_t stride, const float *__restrict__ b, int K)
