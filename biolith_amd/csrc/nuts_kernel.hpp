@@ -49,12 +49,19 @@
 #ifdef BL_STAMPS
 #define BL_STAMP_DECL long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long st_prev = (long long)clock64(); long long st_rt0 = (long long)wall_clock64(); long long st_spins = 0; \
     long long st_kn[3] = {0, 0, 0}, st_kc[3] = {0, 0, 0}; int st_kind = 0; long long st_sub[6] = {0, 0, 0, 0, 0, 0}; long long st_t = 0; \
-    long long st_ae[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int st_ae_cls = -1;
+    long long st_ae[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int st_ae_cls = -1; \
+    long long st_pr[4] = {0, 0, 0, 0}; long long st_bo = 0, st_r0 = 0; bool st_first = true;
+// st_pr: the exchange's first round {issued -> tags checked, barrier open -> tags checked}, the later rounds' cycles, exchanges
+// (st_bo: when the first barrier opened; st_r0: when the round in flight was issued)
+#define BL_STAMP_ROUND0 st_r0 = (long long)clock64();
+#define BL_STAMP_ROUND1 { const long long st_now = (long long)clock64(); st_sub[3] += st_now - st_r0; \
+    if (st_first) { st_pr[0] += st_now - st_r0; st_pr[1] += st_now - st_bo; st_pr[3]++; st_first = false; } else st_pr[2] += st_now - st_r0; }
 // The tick BEHIND a transition's end is a kind of its own (its stamp 0 is end_deferred alone): st_ae holds, for warm-up transitions
 // (class 0) and sampling ones (class 1), {ticks, stamp 0, stamp 1 = the wait for the compute waves, unsuccessful poll rounds}
 #define BL_STAMP(i) { const long long st_now = (long long)clock64(); st_acc[i] += st_now - st_prev; \
     if (st_ae_cls >= 0 && (i) <= 1) { st_ae[st_ae_cls * 4 + 1 + ((i) & 1)] += st_now - st_prev; if ((i) == 0) st_ae[st_ae_cls * 4]++; } \
     if ((i) == 5) st_ae_cls = -1; \
+    if ((i) == 1) { st_bo = st_now; st_first = true; } \
     st_prev = st_now; }
 #define BL_STAMP_AFTER_END(ek) st_ae_cls = ((ek) & 16) ? 1 : (((ek) & 2) ? 0 : -1);
 // critical-control time split by what the tick decided: 0 next leaf of the subtree, 1 next doubling, 2 transition end / init
@@ -68,6 +75,8 @@
 #define BL_SUB0
 #define BL_SUB(i)
 #define BL_COUNT_SPINS(n)
+#define BL_STAMP_ROUND0
+#define BL_STAMP_ROUND1
 #define BL_STAMP_DECL
 #define BL_STAMP(i)
 #define BL_STAMP_KIND(k)
@@ -256,6 +265,30 @@ struct BlSpinBound {
 // follow the one switch.  The host keeps the records' pitch even (biolith_hip.hip), so pairs stay 16-byte aligned.
 #ifndef BL_POLL_PAIRS
 #define BL_POLL_PAIRS 1
+#endif
+// The first poll round of an exchange, issued by the control wave BEFORE the tick's first barrier -- the moment its decisions have kept the
+// evaluation in flight (`redo` false) -- with the prior at the position in flight, the preparation of the speculative position and the
+// barrier itself in the shadow of the loads' latency; the tags are looked at behind the barrier, where the parent issued the loads.  Since
+// the resident records the control wave is the late side of every kind of tick, so that block is serial work on the tick's critical path,
+// and none of its values is needed before the gathered sum exists.  The records are self-validating {epoch, value} granules: a load that
+// is early sees a stale tag (the slot's last use, four epochs back) and is loaded again, nothing else.  The speculating forms with more
+// than one workgroup per chain only (SPEC && multi_wg), in the paired form and in the one-batch 8-byte form; the wide form's batches,
+// occu_rn's forms (there the evaluation is the late side, and the kernel is at its register budget) and the one-workgroup form keep the
+// parent's code.  1: on every tick that keeps its evaluation; 2: only behind decisions that started a new subtree (a doubling's: the long
+// ones, after which every peer's record has long landed); 0, the default: the first round behind the barrier.  Built, measured and NOT
+// kept (profiles/NOTES.md, profiles/poll_early/): the headline kernel ran 3.1 % slower with 1 and 3.4 % slower with 2 -- on a leaf tick
+// the decisions end before the peers' records are visible in L2, the early round misses (rounds per exchange 1.18 -> 1.47) and the full
+// round behind the miss ends later than the parent's one late round; why the selective form loses too was not found.
+#ifndef BL_POLL_EARLY
+#define BL_POLL_EARLY 0
+#endif
+// A round that is not complete reloads only what is missing: every lane keeps the loads whose tags matched (both tags of a pair) and load q
+// is issued again under the predicate "this lane's tags missed" -- the branch over a load that no lane misses is the ballot; completion
+// is `__all` over every load's tags, as before.  A kept value cannot go stale: its slot is rewritten four epochs later and no workgroup
+// runs more than two ahead (BL_XCHG_SLOTS).  Same forms as BL_POLL_EARLY.  1, the default (headline kernel time -1.1 %); 0: every retry
+// loads everything (A/B).
+#ifndef BL_POLL_REFILL
+#define BL_POLL_REFILL 1
 #endif
 __host__ __device__ __forceinline__ constexpr int bl_pair_pos(int v) { return v < 8 ? 2 * v : 2 * (v - 8) + 1; }
 __host__ __device__ __forceinline__ constexpr int bl_pair_lane(int v) { return v < 8 ? v : 24 + v; }
@@ -635,6 +668,47 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
 #define BL_RN_HYBRID 2
 #endif
     constexpr bool HYBRID = BL_RN_HYBRID && LDS && MODEL == 1;
+    // (BL_POLL_EARLY, BL_POLL_REFILL: the speculating forms of more than one workgroup per chain; every other kernel keeps the parent's poll)
+    // (... with at most 4 covariates on a side: the kernels of 8 and 16 sit at the 256-register budget and spill already, three of them
+    // spilled more VGPRs with the round's registers live across the barrier -- profiles/poll_early/resources.txt; and not the dynamic
+    // model's kernels: occu_dyn ran 0.8 % slower with the refill alone, beyond its bar -- profiles/poll_early/ab_secondary.txt)
+    constexpr bool POLL_FORMS = SPEC && multi_wg && KS <= 4 && KO <= 4 && MODEL != 8;
+    constexpr bool POLL_EARLY = BL_POLL_EARLY && POLL_FORMS;
+    constexpr bool POLL_REFILL = BL_POLL_REFILL && POLL_FORMS;
+    // One round of those forms, issued for epoch `ep`.  Paired: four 16-byte sc1 loads; loads beyond ceil(nq / 2) would only re-read
+    // record k - 1 and are skipped wave-uniformly (their tags pass, their values meet pval = 0).  8-byte: load pairs beyond nq are
+    // skipped the same way -- their tags pass, and their VALUES are filled in behind the complete round (poll_fill_one: a copy of load 0,
+    // as the parent had it, so the sums see the same bits; filled in here the copy would wait for load 0 in the middle of the round).
+    auto poll_issue_pairs = [&](BlU4 (&v)[4], unsigned ep) {
+        const int nqp = (nq + 1) >> 1;
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(xbase), (short)0, (int)(BL_XCHG_SLOTS * rec_bytes), 0x00020000);
+        // (the slot's offset is the loads' scalar operand: said to be uniform here, or every load sits in a loop over its distinct values)
+        const int soff = __builtin_amdgcn_readfirstlane((int)((ep & (BL_XCHG_SLOTS - 1u)) * rec_bytes));
+        asm volatile("" ::: "memory"); // (compiler only: every round loads anew)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            if (q < nqp) v[q] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)ppoff[q], soff, 16); // (aux 16: sc1)
+            else v[q] = BlU4{0u, ep, 0u, ep};
+        }
+    };
+    auto poll_issue_one = [&](unsigned long long (&v)[8], unsigned ep) {
+        const unsigned char *rb = xbase + (ep & (BL_XCHG_SLOTS - 1u)) * rec_bytes;
+#pragma unroll
+        for (int q = 0; q < 8; q += 2) {
+            if (q < nq) { // wave-uniform
+                v[q] = bl_poll_load(rb, poff[q]);
+                v[q + 1] = bl_poll_load(rb, poff[q + 1]);
+            } else {
+                v[q] = (unsigned long long)ep << 32;
+                v[q + 1] = (unsigned long long)ep << 32;
+            }
+        }
+    };
+    auto poll_fill_one = [&](unsigned long long (&v)[8]) {
+#pragma unroll
+        for (int q = 2; q < 8; q += 2)
+            if (!(q < nq)) { v[q] = v[0]; v[q + 1] = v[0]; }
+    };
     auto decide = [&]() {
         have_pending = false;
         const double acc = p_acc;
@@ -928,7 +1002,8 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
     int run_status = 0;
     while (true) {
         bool redo = false; // the evaluation in flight is not the one the sampler needs next
-        if ((SPEC || HYBRID) && have_pending) {
+        const bool decided = (SPEC || HYBRID) && have_pending; // (this tick's evaluation runs beside the decisions about the last one)
+        if (decided) {
             end_deferred(); // (only if the guess at a transition's end happened to be right: otherwise done in the branch below)
             decide();
             // was the position being evaluated right now the one just chosen?  (bit-equal or redo: correctness
@@ -950,13 +1025,32 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
             end_deferred(); // beside the evaluation of the new transition's first leaf
             BL_STAMP(0)
         }
-        // What the exchange of the evaluation in flight does not need is done BEFORE the barrier -- on a leaf tick the decisions
-        // are over before the site evaluation is, and this ran in the shadow of nothing: the first poll then goes out the moment the
-        // barrier opens (the prior at the position in flight, which kind of leaf comes next, the peeked direction, the other edge).
+        // What the exchange of the evaluation in flight does not need is done BEFORE the barrier (the prior at the position in flight,
+        // which kind of leaf comes next, the peeked direction, the other edge).  Until the resident records the decisions of a leaf
+        // tick were over before the site evaluation was and this ran in the shadow of nothing; today the control wave is the late
+        // side on every kind of tick.  With BL_POLL_EARLY (measured slower, off by default) the exchange's first round is issued in
+        // front of this block, which then runs, with the barrier, in the shadow of those loads; otherwise the first poll goes out the
+        // moment the barrier opens.
         float pe2 = 0.0f, pg = 0.0f;
         int spec_kind = 0;           // 0 none, 1 next leaf of the subtree, 2 / 3 next doubling from this leaf / from the other edge
         float spec_ed = epsdir, spec_other = 0.0f;
+        BlU4 pv[4];                  // the round in flight: paired form ...
+        unsigned long long ov[8];    // ... and one-batch 8-byte form (the forms of BL_POLL_EARLY / BL_POLL_REFILL only)
+        // (not the wide form's batches; BL_POLL_EARLY 2: only behind decisions that started a new subtree -- the long ones, a doubling's)
+        const bool early = POLL_EARLY && (PAIRS || one_batch) && (BL_POLL_EARLY != 2 || (decided && snprop == 0));
         if (!redo) {
+        if constexpr (POLL_EARLY) {
+            // The first round for epoch + 1, the epoch the compute waves publish the evaluation in flight under: no barrier stands in
+            // front, so this workgroup's own record may be among the missing ones -- a stale tag like any other.  On a `redo` tick
+            // nothing is loaded, as before: every workgroup skips that epoch alike.
+            if (early) {
+                for (int z = 0; z < p.first_delay; z++) __builtin_amdgcn_s_sleep(1);
+                BL_STAMP_ROUND0
+                if (PAIRS) poll_issue_pairs(pv, epoch + 1u);
+                else poll_issue_one(ov, epoch + 1u);
+                BL_STAMP(6)
+            }
+        }
         // ------------------------------------------------ potential at cz (lane d) ----
         // prior of lane d: pe2 = 2 x its energy, pg = d energy / d theta_d
         //   Normal(loc, scale):            pe2 = (theta-loc)^2 / scale^2 ,  pg = (theta-loc) / scale^2
@@ -1024,7 +1118,8 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
             BL_STAMP(2)
             // a first poll that misses costs a whole extra round trip: give the slowest peers' stores
             // a moment to land before looking
-            for (int z = 0; z < p.first_delay; z++) __builtin_amdgcn_s_sleep(1);
+            if (!early)
+                for (int z = 0; z < p.first_delay; z++) __builtin_amdgcn_s_sleep(1);
             double acc = 0.0;
             bool timed_out = false;
             if (!multi_wg) {
@@ -1050,6 +1145,49 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
                         comp = (__hip_atomic_load(cold->abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) ? 1.0f : 0.0f;
                 }
                 acc = (double)comp;
+            } else if (PAIRS && (POLL_EARLY || POLL_REFILL)) {
+                // paired records, the first round already in flight (BL_POLL_EARLY) and retries that reload only what is missing
+                // (BL_POLL_REFILL): the first wait for a load stands HERE, behind the barrier, in front of the tag check
+                const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(xbase), (short)0, (int)(BL_XCHG_SLOTS * rec_bytes), 0x00020000);
+                const int soff = __builtin_amdgcn_readfirstlane((int)((epoch & (BL_XCHG_SLOTS - 1u)) * rec_bytes));
+                BlSpinBound bound;
+                if (!early) {
+                    BL_STAMP_ROUND0
+                    poll_issue_pairs(pv, epoch);
+                }
+                while (true) {
+                    unsigned badq[4], bad = 0u;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        badq[q] = (pv[q].y ^ epoch) | (pv[q].w ^ epoch);
+                        bad |= badq[q];
+                    }
+                    const bool all_in = __all(bad == 0u);
+                    BL_STAMP_ROUND1
+                    if (all_in) break;
+                    if (bound.expired(p.spin_limit)) { timed_out = true; break; }
+                    if (!local)
+                        for (int z = 0; z < p.poll_sleep; z++) __builtin_amdgcn_s_sleep(1);
+                    BL_STAMP_ROUND0
+                    if constexpr (POLL_REFILL) {
+                        asm volatile("" ::: "memory"); // (compiler only: a retry loads anew)
+#pragma unroll
+                        for (int q = 0; q < 4; q++) {
+                            // (the lanes' predicate is the ballot: no lane misses it, the load is branched over; q >= nqp: the
+                            // constant's tags never miss)
+                            if (badq[q] != 0u) pv[q] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)ppoff[q], soff, 16);
+                        }
+                    } else {
+                        poll_issue_pairs(pv, epoch);
+                    }
+                }
+                BL_COUNT_SPINS(bound.spins)
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const auto r = __builtin_amdgcn_permlane32_swap(pv[q].x, pv[q].z, false, false);
+                    acc += (double)(pval[2 * q] * __uint_as_float(r[0]));
+                    acc += (double)(pval[2 * q + 1] * __uint_as_float(r[1]));
+                }
             } else if (PAIRS) {
                 // paired records: four 16-byte sc1 loads per lane and round (see BL_POLL_PAIRS); loads beyond ceil(nq / 2) would only
                 // re-read record k - 1 and are skipped wave-uniformly (their tags pass, their values meet pval = 0)
@@ -1059,9 +1197,7 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
                 BlU4 v[4];
                 BlSpinBound bound;
                 while (true) {
-#ifdef BL_STAMPS
-                    const long long st_r0 = (long long)clock64();
-#endif
+                    BL_STAMP_ROUND0
                     asm volatile("" ::: "memory"); // (compiler only: every round loads anew)
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
@@ -1072,9 +1208,7 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
 #pragma unroll
                     for (int q = 0; q < 4; q++) bad |= (v[q].y ^ epoch) | (v[q].w ^ epoch);
                     const bool all_in = __all(bad == 0u);
-#ifdef BL_STAMPS
-                    st_sub[3] += (long long)clock64() - st_r0; // cycles in poll rounds (loads issued -> tags checked)
-#endif
+                    BL_STAMP_ROUND1 // (cycles in poll rounds: loads issued -> tags checked)
                     if (all_in) break;
                     if (bound.expired(p.spin_limit)) { timed_out = true; break; }
                     if (!local)
@@ -1088,6 +1222,41 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
                     acc += (double)(pval[2 * q] * __uint_as_float(r[0]));
                     acc += (double)(pval[2 * q + 1] * __uint_as_float(r[1]));
                 }
+            } else if (one_batch && (POLL_EARLY || POLL_REFILL)) {
+                // one batch of 8-byte loads, the first round already in flight (BL_POLL_EARLY) and retries that reload only what is
+                // missing (BL_POLL_REFILL); same lanes, same records, same order of the sums as the form below
+                BlSpinBound bound;
+                if (!early) {
+                    BL_STAMP_ROUND0
+                    poll_issue_one(ov, epoch);
+                }
+                while (true) {
+                    unsigned badq[8], bad = 0u;
+#pragma unroll
+                    for (int q = 0; q < 8; q++) {
+                        badq[q] = ((unsigned)(ov[q] >> 32)) ^ epoch;
+                        bad |= badq[q];
+                    }
+                    const bool all_in = __all(bad == 0u);
+                    BL_STAMP_ROUND1
+                    if (all_in) break;
+                    if (bound.expired(p.spin_limit)) { timed_out = true; break; }
+                    if (!local)
+                        for (int z = 0; z < p.poll_sleep; z++) __builtin_amdgcn_s_sleep(1);
+                    BL_STAMP_ROUND0
+                    if constexpr (POLL_REFILL) {
+#pragma unroll
+                        for (int q = 0; q < 8; q++) {
+                            if (badq[q] != 0u) ov[q] = bl_poll_load(rbase, poff[q]); // (q >= nq: the constant's tag never misses)
+                        }
+                    } else {
+                        poll_issue_one(ov, epoch);
+                    }
+                }
+                BL_COUNT_SPINS(bound.spins)
+                poll_fill_one(ov);
+#pragma unroll
+                for (int q = 0; q < 8; q++) acc += (double)(pval[q] * __uint_as_float((unsigned)ov[q]));
             } else if (one_batch) {
                 // common shape: one round of <= 8 loads per lane covers all k records.  (Measured and dropped: two rounds in flight
                 // half a round trip apart, the first complete one taken -- 4-11 % slower: the waits on the second round's loads
@@ -1095,9 +1264,7 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
                 unsigned long long v[8];
                 BlSpinBound bound;
                 while (true) {
-#ifdef BL_STAMPS
-                    const long long st_r0 = (long long)clock64();
-#endif
+                    BL_STAMP_ROUND0
 #pragma unroll
                     for (int q = 0; q < 8; q += 2) {
                         if (q < nq) { // wave-uniform: skip load pairs that would only re-read record k-1
@@ -1112,9 +1279,7 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
 #pragma unroll
                     for (int q = 0; q < 8; q++) bad |= ((unsigned)(v[q] >> 32)) ^ epoch;
                     const bool all_in = __all(bad == 0u);
-#ifdef BL_STAMPS
-                    st_sub[3] += (long long)clock64() - st_r0; // cycles in poll rounds (loads issued -> tags checked)
-#endif
+                    BL_STAMP_ROUND1 // (cycles in poll rounds: loads issued -> tags checked)
                     if (all_in) break;
                     if (bound.expired(p.spin_limit)) { timed_out = true; break; }
                     if (!local)
@@ -1230,6 +1395,7 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
         for (int i = 0; i < 3; i++) { cold->dbg[11 + i] = st_kn[i]; }
         cold->dbg[14] = st_kc[0]; cold->dbg[15] = st_kc[1]; cold->dbg[7] = st_kc[2];
         for (int i = 0; i < 4; i++) cold->dbg[16 + i] = st_sub[i];
+        if constexpr (MODEL != 1) for (int i = 0; i < 4; i++) cold->dbg[22 + i] = st_pr[i]; // (occu_rn keeps its own counters there, below)
     }
     if (cold->dbg && chain == 0 && member < 2 && tid == 0) // the tick behind a transition's end, on workgroup 0 and on one other
         for (int i = 0; i < 8; i++) cold->dbg[544 + member * 8 + i] = st_ae[i];

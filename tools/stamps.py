@@ -14,8 +14,9 @@ os.environ.setdefault("BIOLITH_HIP_LIB", os.path.join(ROOT, "biolith_amd", "lib"
 from biolith_amd.engine import OccuDataset  # noqa: E402
 from biolith_amd.models import simulate  # noqa: E402
 
-NAMES = ["decisions + bookkeeping (under phase A)", "wait for compute waves", "wg partial+publish", "sweep (poll)",
-         "speculative position", "barrier2", "-", "-"]
+NAMES = ["decisions + bookkeeping (under phase A)", "first round issued -> barrier open (prior, speculation's preparation, barrier)",
+         "(slot offset)", "barrier open -> gathered (poll, sums, folds)", "speculative position", "barrier2",
+         "decisions done -> first round issued (BL_POLL_EARLY; 0 without it: the round is issued behind the barrier)"]
 
 
 def main():
@@ -33,13 +34,22 @@ def main():
             mhz = tot / (rt / 100.0) if rt else float("nan")  # s_memrealtime ticks at 100 MHz
             print(f"k={r.wgs_per_chain} chains={chains} kernel {r.kernel_ms:.1f} ms ticks {ticks} "
                   f"cycles/tick {tot / max(ticks, 1):.0f} clock {mhz:.0f} MHz us/tick {r.kernel_ms * 1e3 / max(ticks, 1):.2f} l2local_chains {r.chains_l2_local} poll-rounds/tick {int(c[10]) / max(ticks, 1) + 1:.2f}")
-            for n, v in zip(NAMES[:6], c[:6]):
-                print(f"    {n:40s} {v / max(ticks, 1):8.0f} cyc  {100.0 * v / tot:5.1f} %")
+            for i in (0, 6, 1, 2, 3, 4, 5):  # (in the order the control wave passes them)
+                print(f"    {NAMES[i]:40s} {c[i] / max(ticks, 1):8.0f} cyc  {100.0 * c[i] / tot:5.1f} %")
             kn = c[11:14].astype(float)
             kc = np.array([c[14], c[15], c[7]], dtype=float)
             print(f"    site evaluation (compute wave 1): {int(c[20])} passes, {c[21] / max(float(c[20]), 1.0):.0f} cyc each")
             rounds = float(c[10]) + ticks
-            print(f"    poll rounds: {rounds / max(ticks, 1):.2f} per exchange, {c[19] / max(rounds, 1.0):.0f} cyc each (loads issued -> tags checked)")
+            print(f"    poll rounds: {rounds / max(ticks, 1):.2f} per tick, {c[19] / max(rounds, 1.0):.0f} cyc each (loads issued -> tags checked)")
+            # first and later rounds apart (the plain-model kernels; occu_rn's build keeps its own counters in these slots): exchanges are
+            # the ticks that were not dropped; a first round issued in front of the barrier is partly hidden behind the preparation and
+            # the barrier -- what is left of it on the critical path is "barrier open -> first tags checked"
+            nx, later = float(c[25]), float(c[10])
+            if nx > 0:
+                hidden = f" (hidden in front of it {(c[22] - c[23]) / nx:.0f})" if c[6] > 0 else " (the round is issued behind it)"
+                print(f"    exchanges {int(nx)} ({100 * nx / max(ticks, 1):.1f} % of ticks), rounds per exchange {1 + later / nx:.3f}; first round: issued -> tags checked "
+                      f"{c[22] / nx:.0f} cyc; barrier open -> first tags checked {c[23] / nx:.0f}{hidden}; a later round "
+                      f"{c[24] / max(later, 1.0):.0f} cyc ({int(later)} of them)")
             n_end = max(float(c[13]), 1.0)
             print("    transition end, per tick: flush bookkeeping %.0f | select/adapt/output %.0f | new momentum+tree %.0f cyc"
                   % (c[16] / n_end, c[17] / n_end, c[18] / n_end))
