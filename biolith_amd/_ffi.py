@@ -78,7 +78,7 @@ EXPORTS = (
     "bl_nuts_env_overrides", "bl_env_overrides", "bl_site_posterior", "bl_abundance_posterior", "bl_path_posterior",
     "bl_score_posterior", "bl_count_posterior", "bl_predict_comb", "bl_deterministic_comb", "bl_predictive_check",
     "bl_predictive_density", "bl_psis_loo", "bl_predictive_check_counts", "bl_site_summary", "bl_regional_totals",
-    "bl_site_diagnostics", "bl_response_curves",
+    "bl_site_diagnostics", "bl_response_curves", "bl_trajectory_totals",
 )
 
 _lib = None
@@ -165,6 +165,7 @@ def load():
         L.bl_site_diagnostics.argtypes = [vp, C.c_int, fp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp]
         L.bl_regional_totals.argtypes = [vp, C.c_int, fp, C.c_uint64, C.c_int, C.POINTER(C.c_int32), dp, dp, dp]
         L.bl_response_curves.argtypes = [vp, C.c_int, fp, C.c_int, C.c_int, C.c_int, fp, dp, dp]
+        L.bl_trajectory_totals.argtypes = [vp, C.c_int, fp, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_int32), dp] + [dp] * 7
         L.bl_psis_loo.argtypes = [C.c_int, C.c_int, C.c_int64, fp, C.c_int64, dp, dp, dp]
         L.bl_site_posterior.argtypes = [vp, C.c_int, fp, C.c_uint64, fp, fp, C.POINTER(C.c_uint8)]
         L.bl_abundance_posterior.argtypes = [vp, C.c_int, fp, C.c_uint64, fp, fp, fp, C.POINTER(C.c_int32)]

@@ -35,6 +35,7 @@
 #include "site_diagnostics.hpp"
 #include "regional_totals.hpp"
 #include "response_curves.hpp"
+#include "trajectory_totals.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -2545,26 +2546,25 @@ extern "C" int bl_site_diagnostics(bl_dataset *ds, int n_draws, const float *dra
 // 64-lane waves (regional_totals.hpp).  run_over_draws cuts the draws so that the workspace and the chunk's totals stay within its 256 MB
 // each (BL_TOTALS_WORKSPACE_BYTES says so in the header).
 static_assert(BL_TOTALS_WORKSPACE_BYTES == (256u << 20), "bl_regional_totals states run_over_draws' bound");
-extern "C" int bl_regional_totals(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, int n_regions, const int32_t *region,
-                                  const double *weight, double *site_total, double *latent_total)
+
+// The slots of the totals' kernels (regional_totals.hpp, trajectory_totals.hpp), checked, laid out and taken to the device for `entry`.
+struct RegionSlots {
+    int n_waves = 0;
+    int *site = nullptr, *wave_first = nullptr; // device; scratch's
+    double *w = nullptr;                        // device, NULL without weights
+};
+static int region_slots(const char *entry, int N, int G, const int32_t *region, const double *weight, DevScratch &scratch, RegionSlots &out)
 {
-    int rc = per_draw_front("bl_regional_totals", ds, n_draws, draws, (site_total || latent_total) && region,
-                            [](const bl_dataset *d) {
-                                return d->nsp == 1 && ((d->model >= 0 && d->model <= 4) || re_kind_in(d, {0, 1, 2, 3, 4, 5, 6, 7}));
-                            },
-                            "occu, occu_cs, occu_cop, occu_rn and nmixture: the handles of bl_predict, bl_predict_counts and bl_predict_scores");
-    if (rc) return rc;
-    const int N = ds->dims.n_sites, T = ds->dims.n_periods, G = n_regions;
-    if (G < 1) return bl_fail(BL_ERR_INVALID, "bl_regional_totals: n_regions=%d, at least 1", G);
+    if (G < 1) return bl_fail(BL_ERR_INVALID, "%s: n_regions=%d, at least 1", entry, G);
     std::vector<int> wave_first((size_t)G + 1, 0);
     for (int i = 0; i < N; i++) {
         if (region[i] < -1 || region[i] >= G)
-            return bl_fail(BL_ERR_INVALID, "bl_regional_totals: region[%d]=%d outside -1 .. n_regions - 1 = %d", i, (int)region[i], G - 1);
-        if (weight && !std::isfinite(weight[i])) return bl_fail(BL_ERR_INVALID, "bl_regional_totals: weight[%d]=%g is not finite", i, weight[i]);
+            return bl_fail(BL_ERR_INVALID, "%s: region[%d]=%d outside -1 .. n_regions - 1 = %d", entry, i, (int)region[i], G - 1);
+        if (weight && !std::isfinite(weight[i])) return bl_fail(BL_ERR_INVALID, "%s: weight[%d]=%g is not finite", entry, i, weight[i]);
         if (region[i] >= 0) wave_first[(size_t)region[i] + 1]++; // (the region's sites for now)
     }
     if ((size_t)N + (size_t)63 * G > (size_t)INT_MAX)
-        return bl_fail(BL_ERR_UNSUPPORTED, "bl_regional_totals: %d sites in %d regions need more than 2^31 slots", N, G);
+        return bl_fail(BL_ERR_UNSUPPORTED, "%s: %d sites in %d regions need more than 2^31 slots", entry, N, G);
     for (int g = 0; g < G; g++) wave_first[(size_t)g + 1] = wave_first[g] + (wave_first[(size_t)g + 1] + 63) / 64;
     const int W = wave_first[G];
     std::vector<int> slot_site((size_t)W * 64, -1), cursor(G);
@@ -2576,6 +2576,32 @@ extern "C" int bl_regional_totals(bl_dataset *ds, int n_draws, const float *draw
         slot_site[s] = i;
         if (weight) slot_w[s] = weight[i];
     }
+    out.n_waves = W;
+    BL_HIP(scratch.alloc((void **)&out.site, slot_site.size() * 4));
+    BL_HIP(scratch.alloc((void **)&out.wave_first, wave_first.size() * 4));
+    BL_HIP(hipMemcpy(out.site, slot_site.data(), slot_site.size() * 4, hipMemcpyHostToDevice));
+    BL_HIP(hipMemcpy(out.wave_first, wave_first.data(), wave_first.size() * 4, hipMemcpyHostToDevice));
+    if (weight) {
+        BL_HIP(scratch.alloc((void **)&out.w, slot_w.size() * 8));
+        BL_HIP(hipMemcpy(out.w, slot_w.data(), slot_w.size() * 8, hipMemcpyHostToDevice));
+    }
+    return BL_OK;
+}
+
+extern "C" int bl_regional_totals(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, int n_regions, const int32_t *region,
+                                  const double *weight, double *site_total, double *latent_total)
+{
+    int rc = per_draw_front("bl_regional_totals", ds, n_draws, draws, (site_total || latent_total) && region,
+                            [](const bl_dataset *d) {
+                                return d->nsp == 1 && ((d->model >= 0 && d->model <= 4) || re_kind_in(d, {0, 1, 2, 3, 4, 5, 6, 7}));
+                            },
+                            "occu, occu_cs, occu_cop, occu_rn and nmixture: the handles of bl_predict, bl_predict_counts and bl_predict_scores");
+    if (rc) return rc;
+    const int N = ds->dims.n_sites, T = ds->dims.n_periods, G = n_regions;
+    DevScratch scratch;
+    RegionSlots slots;
+    if ((rc = region_slots("bl_regional_totals", N, G, region, weight, scratch, slots))) return rc;
+    const int W = slots.n_waves;
 
     BlRegionalTotalsParams p{};
     p.rows = ds->d_rows; p.ns = ds->n_stride; p.N = N; p.T = T; p.Ks = ds->Ks; p.D = ds->D;
@@ -2583,18 +2609,7 @@ extern "C" int bl_regional_totals(bl_dataset *ds, int n_draws, const float *draw
     p.seed = (unsigned long long)seed;
     p.n_slots = W * 64; p.n_waves = W; p.n_regions = G;
     p.site_rows = site_total ? 1 : 0; p.latent_rows = latent_total ? T : 0;
-    DevScratch scratch;
-    int *d_site = nullptr, *d_first = nullptr;
-    double *d_w = nullptr;
-    BL_HIP(scratch.alloc((void **)&d_site, slot_site.size() * 4));
-    BL_HIP(scratch.alloc((void **)&d_first, wave_first.size() * 4));
-    BL_HIP(hipMemcpy(d_site, slot_site.data(), slot_site.size() * 4, hipMemcpyHostToDevice));
-    BL_HIP(hipMemcpy(d_first, wave_first.data(), wave_first.size() * 4, hipMemcpyHostToDevice));
-    if (weight) {
-        BL_HIP(scratch.alloc((void **)&d_w, slot_w.size() * 8));
-        BL_HIP(hipMemcpy(d_w, slot_w.data(), slot_w.size() * 8, hipMemcpyHostToDevice));
-    }
-    p.slot_site = d_site; p.slot_w = d_w; p.wave_first = d_first;
+    p.slot_site = slots.site; p.slot_w = slots.w; p.wave_first = slots.wave_first;
     const size_t rows = (size_t)p.site_rows + p.latent_rows;
     const DrawOut outs[] = {{site_total, (size_t)G * 8, (void **)&p.site_total, false},
                             {latent_total, (size_t)T * G * 8, (void **)&p.latent_total, false},
@@ -2648,6 +2663,44 @@ extern "C" int bl_response_curves(bl_dataset *ds, int n_draws, const float *draw
     const size_t per_draw = (size_t)V * p.n_runs * 8; // the workspace's bytes a draw (>= the totals')
     const DrawOut outs[] = {{curve_total, (size_t)V * 8, (void **)&p.total, false}, {nullptr, per_draw, (void **)&p.part, true}};
     return run_over_draws(ds, n_draws, draws, per_draw, outs, p, bl_launch_response_curves);
+}
+
+// ---- trajectory totals: per draw of an occu_dyn handle and region the weighted totals of the occupancy over the seasons, fused ----
+// (BUILDER-DEFINED, like the model.)  Kernels: trajectory_totals.hip.  They read the site covariates at the head of the handle's rows and
+// no visit; T is the call's.  The slots, the workspace and the chunking of the draws are bl_regional_totals'.
+static_assert(BL_TT_MAX_KS == BL_DYN_MAX_KS, "trajectory_totals.hip stages the site covariates an occu_dyn handle takes");
+extern "C" int bl_trajectory_totals(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, int n_periods, int n_regions,
+                                    const int32_t *region, const double *weight, double *occupancy, double *colonised, double *extinct,
+                                    double *equilibrium, double *z, double *z_colonised, double *z_extinct)
+{
+    double *const host[BL_TT_OUTPUTS] = {occupancy, colonised, extinct, equilibrium, z, z_colonised, z_extinct};
+    const bool any = std::any_of(host, host + BL_TT_OUTPUTS, [](const double *h) { return h != nullptr; });
+    int rc = per_draw_front("bl_trajectory_totals", ds, n_draws, draws, any && region,
+                            [](const bl_dataset *d) { return d->model == 8; },
+                            "occu_dyn only; the static models' totals are bl_regional_totals");
+    if (rc) return rc;
+    const int N = ds->dims.n_sites, T = n_periods, G = n_regions;
+    if (T < 1) return bl_fail(BL_ERR_INVALID, "bl_trajectory_totals: n_periods=%d, at least 1", T);
+    if (T > (INT_MAX - 1) / 6) return bl_fail(BL_ERR_UNSUPPORTED, "bl_trajectory_totals: n_periods=%d, at most %d", T, (INT_MAX - 1) / 6);
+    DevScratch scratch;
+    RegionSlots slots;
+    if ((rc = region_slots("bl_trajectory_totals", N, G, region, weight, scratch, slots))) return rc;
+    const int W = slots.n_waves;
+
+    BlTrajectoryTotalsParams p{};
+    p.rows = ds->d_rows; p.ns = ds->n_stride; p.N = N; p.T = T; p.Ks = ds->Ks; p.D = ds->D;
+    p.seed = (unsigned long long)seed;
+    p.n_slots = W * 64; p.n_waves = W; p.n_regions = G;
+    p.slot_site = slots.site; p.slot_w = slots.w; p.wave_first = slots.wave_first;
+    const int rows_of[BL_TT_OUTPUTS] = {T, T - 1, T - 1, 1, T, T - 1, T - 1};
+    for (int k = 0; k < BL_TT_OUTPUTS; k++) p.row_first[k + 1] = p.row_first[k] + (host[k] ? rows_of[k] : 0);
+    const size_t rows = (size_t)p.row_first[BL_TT_OUTPUTS];
+    if (!rows) return BL_OK; // (T = 1 and per-pair outputs alone: they are empty)
+    DrawOut outs[BL_TT_OUTPUTS + 1];
+    for (int k = 0; k < BL_TT_OUTPUTS; k++)
+        outs[k] = DrawOut{host[k], (size_t)(p.row_first[k + 1] - p.row_first[k]) * G * 8, (void **)&p.out[k], false};
+    outs[BL_TT_OUTPUTS] = DrawOut{nullptr, rows * W * 8, (void **)&p.part, true};
+    return run_over_draws(ds, n_draws, draws, rows * std::max(W, G) * 8, outs, p, bl_launch_trajectory_totals);
 }
 
 // ------------------------------------------------------- multi-GPU: the gather of the draws over RCCL ----

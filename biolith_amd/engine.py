@@ -561,6 +561,35 @@ class OccuDataset:
         _ffi.check(self._lib.bl_response_curves(self._h, n, _fp(d), int(side), int(covariate), int(v.size), _fp(v), _dp(w), _dp(out)))
         return out
 
+    TRAJECTORY_OUTPUTS = ("occupancy", "colonised", "extinct", "equilibrium", "z", "z_colonised", "z_extinct")   # the C-ABI's order
+
+    def trajectory_totals(self, draws, region, n_regions: int, n_periods: int, weight=None, seed: int = 0, outputs=TRAJECTORY_OUTPUTS):
+        """Per draw of draws (n, D) of an occu_dyn handle and region, the weighted totals of the occupancy trajectory over
+        ``n_periods`` = T seasons without the observations, fused on the device (BUILDER-DEFINED): a dict of float64 arrays under the
+        names in ``outputs`` -- ``occupancy`` and ``z`` (n, T, n_regions), ``colonised``, ``extinct``, ``z_colonised`` and
+        ``z_extinct`` (n, T - 1, n_regions), ``equilibrium`` (n, n_regions).  T is the call's, not the handle's: the kernel reads the
+        site covariates and no visit.  ``region`` (N,) holds 0 .. n_regions - 1, -1 = in no region; ``weight`` (N,) finite float64,
+        ``None`` = 1.  The terms are float64 throughout, the ``z`` totals those of one ancestral path per draw, a function of (seed,
+        draw, T, period, site), summed in ``regional_totals``' fixed order (include/biolith_hip.h: bl_trajectory_totals).  Nothing of
+        size (n, T, N) exists on the device or the host."""
+        d = self._draw_matrix(draws)
+        n, G, T = d.shape[0], int(n_regions), int(n_periods)
+        r = np.ascontiguousarray(np.asarray(region).reshape(-1), dtype=np.int32)
+        w = None if weight is None else np.ascontiguousarray(np.asarray(weight, dtype=np.float64).reshape(-1))
+        unknown = [k for k in outputs if k not in self.TRAJECTORY_OUTPUTS]
+        if unknown or not outputs:
+            raise ValueError(f"trajectory_totals(): outputs must name some of {self.TRAJECTORY_OUTPUTS}, got {tuple(outputs)}")
+        if n == 0:
+            raise ValueError("trajectory_totals(): no draws")
+        if r.size != self.N or (w is not None and w.size != self.N):
+            raise ValueError(f"trajectory_totals(): region and weight hold one entry per site ({self.N})")
+        rows = dict(occupancy=T, colonised=T - 1, extinct=T - 1, z=T, z_colonised=T - 1, z_extinct=T - 1)   # (T < 1: the C-ABI refuses it)
+        out = {k: np.empty((n, G) if k == "equilibrium" else (n, max(rows[k], 0), G)) for k in self.TRAJECTORY_OUTPUTS if k in outputs}
+        _ffi.check(self._lib.bl_trajectory_totals(self._h, n, _fp(d), C.c_uint64(int(seed) & (2 ** 64 - 1)), T, G,
+                                                  r.ctypes.data_as(C.POINTER(C.c_int32)), _dp(w),
+                                                  *[_dp(out.get(k)) for k in self.TRAJECTORY_OUTPUTS]))
+        return out
+
     def _per_draw(self, fn, draws, seed, outs, pinned=True):
         """Calls a per-draw entry ``fn(handle, n, draws, seed, *outputs)`` for draws (n, D).  ``outs`` lists (wanted, shape behind
         the draw axis, dtype) per output; returns the arrays, ``None`` where not wanted.  With ``pinned`` the 4-byte outputs come from

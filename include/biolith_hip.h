@@ -459,6 +459,42 @@ int bl_response_curves(bl_dataset *ds, int n_draws, const float *draws, int side
                        double *curve_total /* [n_draws][n_values] */);
 
 /*
+ * The posterior of the occupancy trajectory's totals over sets of sites, fused -- BUILDER-DEFINED, like the model (bl_dataset_create_dyn):
+ * per posterior draw of an occu_dyn handle and region, the weighted totals of the occupancy over n_periods seasons WITHOUT the
+ * observations (bl_path_posterior gives the path given them), without an array [n_draws][n_periods][N] ever being stored.  The kernel
+ * reads the site covariates at the head of the handle's rows and no visit; n_periods = T is an argument of the call, not the handle's:
+ * the model is homogeneous in time, so a T beyond the fitted seasons is the forecast.  region, weight and n_regions are
+ * bl_regional_totals'.  A draw is [b_psi | b_col | b_ext (Ks + 1 each) | alpha], as the sampler lays it out.  Per draw n and site i, in
+ * float64 throughout (covariates, NaN -> 0, and coefficients are promoted from float32):
+ *   eta      = fma(x_K, b_K, .. fma(x_1, b_1, b_0)) in covariate order, the intercept first, for each of psi, gamma (colonisation), eps
+ *   rates    e = exp(-|eta|), r = 1 / (1 + e), s = e r; (sigma(eta), sigma(-eta)) = eta > 0 ? (r, s) : (s, r): a rate and its complement
+ *            each come from the sigmoid, no complement is formed as 1 - x
+ *   pi_0 = psi, q_0 = 1 - psi;   col_t = q_t gamma, ext_t = pi_t eps;   pi_t+1 = fma(pi_t, 1 - eps, col_t), q_t+1 = fma(q_t, 1 - gamma, ext_t)
+ *   the path: cell (n, t, i) takes the first uniform u of the generator of cell (n, t of T, i of N) -- csrc/pred_rng.hpp, n the absolute
+ *            draw index, i the site's own index --: z_0 = (double)u < psi, z_t+1 = (double)u < (z_t ? 1 - eps : gamma)
+ * and the outputs, float64 on the host, each a sum over the sites of region g of weight_i times
+ *   occupancy    [n][T][g]      pi_t                          z            [n][T][g]      z_t
+ *   colonised    [n][T - 1][g]  col_t                         z_colonised  [n][T - 1][g]  [z_t = 0, z_t+1 = 1]
+ *   extinct      [n][T - 1][g]  ext_t                         z_extinct    [n][T - 1][g]  [z_t = 1, z_t+1 = 0]
+ *   equilibrium  [n][g]         gamma / (gamma + eps)
+ * NULL = skip (all seven NULL: BL_ERR_INVALID); a skipped output never changes another, with the three z outputs NULL no generator is
+ * touched, and with T = 1 the per-pair outputs are empty and left alone.  A region without a site comes back 0.  The first T rows of
+ * occupancy, colonised and extinct do not depend on n_periods; the path does (the cell's index holds T).
+ * Order and workspace are bl_regional_totals': every product in float64, region g's sites in site order cut into runs of 64, the last
+ * filled up with -0.0, a run summed as the tree (x_l + x_{l+32}), then lanes 16, 8, 4, 2, 1 apart, the runs' sums added in run order, no
+ * atomics; row g is a function of region g's own sites, their weights and the draws, however the draws are chunked and whichever
+ * outputs are asked for, and two calls return the same bytes.  The device holds one double per (draw of a chunk, output row, run of 64)
+ * and per (draw of a chunk, output row, region), at most BL_TOTALS_WORKSPACE_BYTES each -- or one draw's rows --, whatever n_draws is.
+ * Refused with BL_ERR_INVALID, the message holding the offending value: n_periods < 1; n_regions < 1; a label outside
+ * -1 .. n_regions - 1; a non-finite weight; region NULL.  Every output is untouched on any refusal.  Serves handles of
+ * bl_dataset_create_dyn -- one whose every visit is masked included --; every other handle: BL_ERR_UNSUPPORTED, the message names the
+ * model.  BL_ERR_BUSY while a NUTS launch is in flight on the handle.
+ */
+int bl_trajectory_totals(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, int n_periods, int n_regions,
+                         const int32_t *region, const double *weight /* [N], NULL = 1 */, double *occupancy, double *colonised,
+                         double *extinct, double *equilibrium, double *z, double *z_colonised, double *z_extinct);
+
+/*
  * Posterior predictive draws of the discrete sites, one per posterior draw -- what
  * numpyro.infer.Predictive(model_fn, posterior_samples)(key, site_covs, obs_covs) samples in
  * biolith/utils/predict.py:66-92 (obs withheld, so no observation is masked):
