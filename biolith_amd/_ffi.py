@@ -18,6 +18,7 @@ RNG_STREAMS_PER_CHAIN = 64
 MAX_COVS = 16
 PSIS_MAX_DRAWS = 8192   # BL_PSIS_MAX_DRAWS of include/biolith_hip.h
 SUMMARY_MAX_RANKS = 16   # BL_SUMMARY_MAX_RANKS of include/biolith_hip.h
+RICHNESS_MAX_SPECIES = 32   # BL_RICHNESS_MAX_SPECIES of include/biolith_hip.h
 
 
 class EngineError(RuntimeError):
@@ -78,7 +79,7 @@ EXPORTS = (
     "bl_nuts_env_overrides", "bl_env_overrides", "bl_site_posterior", "bl_abundance_posterior", "bl_path_posterior",
     "bl_score_posterior", "bl_count_posterior", "bl_predict_comb", "bl_deterministic_comb", "bl_predictive_check",
     "bl_predictive_density", "bl_psis_loo", "bl_predictive_check_counts", "bl_site_summary", "bl_regional_totals",
-    "bl_site_diagnostics", "bl_response_curves", "bl_trajectory_totals",
+    "bl_site_diagnostics", "bl_response_curves", "bl_trajectory_totals", "bl_species_richness",
 )
 
 _lib = None
@@ -166,6 +167,7 @@ def load():
         L.bl_regional_totals.argtypes = [vp, C.c_int, fp, C.c_uint64, C.c_int, C.POINTER(C.c_int32), dp, dp, dp]
         L.bl_response_curves.argtypes = [vp, C.c_int, fp, C.c_int, C.c_int, C.c_int, fp, dp, dp]
         L.bl_trajectory_totals.argtypes = [vp, C.c_int, fp, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_int32), dp] + [dp] * 7
+        L.bl_species_richness.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, C.POINTER(C.c_int32), dp, dp, dp, dp, dp]
         L.bl_psis_loo.argtypes = [C.c_int, C.c_int, C.c_int64, fp, C.c_int64, dp, dp, dp]
         L.bl_site_posterior.argtypes = [vp, C.c_int, fp, C.c_uint64, fp, fp, C.POINTER(C.c_uint8)]
         L.bl_abundance_posterior.argtypes = [vp, C.c_int, fp, C.c_uint64, fp, fp, fp, C.POINTER(C.c_int32)]

@@ -36,6 +36,7 @@
 #include "regional_totals.hpp"
 #include "response_curves.hpp"
 #include "trajectory_totals.hpp"
+#include "species_richness.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -390,14 +391,16 @@ struct DrawOut {
 
 // Runs launch(d_draws, n0, n1, grid_y) over the draws [n0, n1) in chunks of at most 256 MB / chunk_bytes draws (chunk_bytes: the entry's
 // largest output of one draw), grid_y = min(n1 - n0, 1024) rows of draws, and copies every wanted output back to host + n0 * bytes.
+// A draw is `width` floats, 0 = the handle's D (bl_species_richness stacks its species' blocks: n_species D).
 template <size_t K, class Launch>
 static int run_over_draws(const bl_dataset *ds, int n_draws, const float *draws, size_t chunk_bytes, const DrawOut (&outs)[K],
-                          Launch launch)
+                          Launch launch, size_t width = 0)
 {
     DevScratch scratch;
     float *d_draws = nullptr;
-    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * ds->D * 4));
-    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * ds->D * 4, hipMemcpyHostToDevice));
+    if (!width) width = (size_t)ds->D;
+    BL_HIP(scratch.alloc((void **)&d_draws, (size_t)n_draws * width * 4));
+    BL_HIP(hipMemcpy(d_draws, draws, (size_t)n_draws * width * 4, hipMemcpyHostToDevice));
     const size_t fit = ((size_t)256 << 20) / std::max<size_t>(1, chunk_bytes); // draws whose largest output fills 256 MB
     const int chunk = (int)std::min<size_t>((size_t)n_draws, std::max<size_t>(1, fit));
     for (const DrawOut &o : outs) {
@@ -2701,6 +2704,55 @@ extern "C" int bl_trajectory_totals(bl_dataset *ds, int n_draws, const float *dr
         outs[k] = DrawOut{host[k], (size_t)(p.row_first[k + 1] - p.row_first[k]) * G * 8, (void **)&p.out[k], false};
     outs[BL_TT_OUTPUTS] = DrawOut{nullptr, rows * W * 8, (void **)&p.part, true};
     return run_over_draws(ds, n_draws, draws, rows * std::max(W, G) * 8, outs, p, bl_launch_trajectory_totals);
+}
+
+// ---- species richness: per site the pmf of the number of species present and its expectation over the draws, per draw and region the
+// weighted area holding exactly r species, fused ----
+// (BUILDER-DEFINED, no counterpart in the reference.)  Kernels: species_richness.hip.  They read the site covariates at the head of ONE
+// species' handle and the draws of all of them, stacked (run_over_draws' width: n_species D).  The area side's slots, workspace and
+// chunking are bl_regional_totals'; the site side is one launch over all the draws when they are up, as bl_site_summary's, done before
+// run_over_draws lets go of them.
+extern "C" int bl_species_richness(bl_dataset *ds, int n_species, int n_draws, const float *draws, int n_regions, const int32_t *region,
+                                   const double *weight, double *site_pmf, double *site_expected_mean, double *site_expected_sd,
+                                   double *area_total)
+{
+    const bool site = site_pmf || site_expected_mean || site_expected_sd;
+    int rc = per_draw_front("bl_species_richness", ds, n_draws, draws, (site || area_total) && (region || !area_total), serves_occu,
+                            "occu, with or without false positives / random effects, one handle for all the species");
+    if (rc) return rc;
+    const int N = ds->dims.n_sites, S = n_species, G = n_regions;
+    if (S < 1) return bl_fail(BL_ERR_INVALID, "bl_species_richness: n_species=%d, at least 1", S);
+    if (S > BL_RICHNESS_MAX_SPECIES)
+        return bl_fail(BL_ERR_UNSUPPORTED, "bl_species_richness: n_species=%d above BL_RICHNESS_MAX_SPECIES=%d", S, BL_RICHNESS_MAX_SPECIES);
+    DevScratch scratch;
+    RegionSlots slots;
+    if (area_total && (rc = region_slots("bl_species_richness", N, G, region, weight, scratch, slots))) return rc;
+    const int W = slots.n_waves;
+
+    BlSpeciesRichnessParams p{};
+    p.rows = ds->d_rows; p.ns = ds->n_stride; p.N = N; p.Ks = ds->Ks; p.D = ds->D; p.S = S; p.c = draw_coords(ds);
+    p.n_draws = n_draws;
+    p.n_slots = W * 64; p.n_waves = W; p.n_regions = G;
+    p.slot_site = slots.site; p.slot_w = slots.w; p.wave_first = slots.wave_first;
+    double *const host[3] = {site_pmf, site_expected_mean, site_expected_sd};
+    double **const dev[3] = {&p.pmf, &p.mean, &p.sd};
+    const size_t cells[3] = {(size_t)N * (S + 1), (size_t)N, (size_t)N};
+    for (int k = 0; k < 3; k++)
+        if (host[k]) BL_HIP(scratch.alloc((void **)dev[k], cells[k] * 8));
+    const size_t rows = area_total ? (size_t)S + 1 : 0;
+    const DrawOut outs[] = {{area_total, rows * G * 8, (void **)&p.area_total, false}, {nullptr, rows * W * 8, (void **)&p.part, true}};
+    rc = run_over_draws(ds, n_draws, draws, rows * std::max(W, G) * 8, outs, [&](const float *d_draws, int n0, int n1, int grid_y) {
+        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
+        int e = 0;
+        if (site && n0 == 0) e = bl_launch_species_richness_site(&p, nullptr);
+        if (!e && area_total) e = bl_launch_species_richness_area(&p, grid_y, nullptr);
+        if (!e && n1 == n_draws) e = (int)hipStreamSynchronize(nullptr); // the site kernel reads all the draws
+        return (hipError_t)e;
+    }, (size_t)S * ds->D);
+    if (rc) return rc;
+    for (int k = 0; k < 3; k++)
+        if (host[k]) BL_HIP(hipMemcpy(host[k], *dev[k], cells[k] * 8, hipMemcpyDeviceToHost));
+    return BL_OK;
 }
 
 // ------------------------------------------------------- multi-GPU: the gather of the draws over RCCL ----

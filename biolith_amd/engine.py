@@ -590,6 +590,45 @@ class OccuDataset:
                                                   *[_dp(out.get(k)) for k in self.TRAJECTORY_OUTPUTS]))
         return out
 
+    def species_richness(self, draws, region=None, n_regions: int = 0, weight=None, site: bool = True, area: bool = True):
+        """The posterior of the number of species present, for draws (n, S, D) of S species sampled under one chain -- block ``s`` of a
+        draw is species ``s``'s draw for THIS handle, whose site covariates are every species' --, fused on the device
+        (BUILDER-DEFINED): ``pmf, expected_mean, expected_sd, area``, float64, ``None`` where not wanted.  Given a draw the species'
+        presences at a site are independent Bernoulli(``psi_s``), ``psi_s`` ``deterministic``'s float32 value bit for bit, so their
+        number is Poisson-binomial; its pmf is a float64 recursion over the species in ascending order.  With ``site``: ``pmf``
+        (N, S + 1) the pmf averaged over the draws, ``expected_mean`` and ``expected_sd`` (N,) the mean and sd (ddof 1, NaN for one
+        draw) of ``sum_s psi_s`` over the draws, every sum in draw order.  With ``area``: (n, S + 1, n_regions), row ``r`` the
+        weighted area holding exactly ``r`` species, summed in ``regional_totals``' fixed order; ``region`` (N,) holds
+        0 .. n_regions - 1, -1 = in no region, ``weight`` (N,) finite float64, ``None`` = 1; both are read for ``area`` alone
+        (include/biolith_hip.h: bl_species_richness).  Nothing of size (n, N) exists on the device or the host."""
+        d = np.asarray(draws, dtype=np.float32)
+        if d.ndim != 3 or d.shape[-1] != self.D:
+            raise ValueError(f"species_richness(): draws must be (n, n_species, {self.D}) for this dataset, got shape {d.shape}")
+        d = np.ascontiguousarray(d)
+        n, S = d.shape[0], d.shape[1]
+        if not (site or area):
+            raise ValueError("species_richness(): neither the site outputs nor the area is wanted")
+        if n == 0:
+            raise ValueError("species_richness(): no draws")
+        if S > _ffi.RICHNESS_MAX_SPECIES:
+            raise NotImplementedError(f"species_richness(): {S} species, at most {_ffi.RICHNESS_MAX_SPECIES} (BL_RICHNESS_MAX_SPECIES)")
+        r = w = None
+        G = int(n_regions)
+        if area:
+            if region is None:
+                raise ValueError("species_richness(): the area needs region")
+            r = np.ascontiguousarray(np.asarray(region).reshape(-1), dtype=np.int32)
+            w = None if weight is None else np.ascontiguousarray(np.asarray(weight, dtype=np.float64).reshape(-1))
+            if r.size != self.N or (w is not None and w.size != self.N):
+                raise ValueError(f"species_richness(): region and weight hold one entry per site ({self.N})")
+        pmf = np.empty((self.N, S + 1)) if site else None
+        mean = np.empty(self.N) if site else None
+        sd = np.empty(self.N) if site else None
+        out_area = np.empty((n, S + 1, max(G, 0))) if area else None
+        _ffi.check(self._lib.bl_species_richness(self._h, S, n, _fp(d), G, None if r is None else r.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 _dp(w), _dp(pmf), _dp(mean), _dp(sd), _dp(out_area)))
+        return pmf, mean, sd, out_area
+
     def _per_draw(self, fn, draws, seed, outs, pinned=True):
         """Calls a per-draw entry ``fn(handle, n, draws, seed, *outputs)`` for draws (n, D).  ``outs`` lists (wanted, shape behind
         the draw axis, dtype) per output; returns the arrays, ``None`` where not wanted.  With ``pinned`` the 4-byte outputs come from

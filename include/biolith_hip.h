@@ -495,6 +495,43 @@ int bl_trajectory_totals(bl_dataset *ds, int n_draws, const float *draws, uint64
                          double *extinct, double *equilibrium, double *z, double *z_colonised, double *z_extinct);
 
 /*
+ * The posterior of species richness -- how many of the species that were sampled under one chain a site holds --, fused --
+ * BUILDER-DEFINED (the reference has no counterpart; its users would form predict()'s psi [n_draws][T][N][S] and run a recursion over
+ * the species per draw and site on the host).  ds is ONE single-species occu handle; its site covariates are every species'.  draws is
+ * stacked, [n_draws][n_species][D] float32 on the host, D the handle's: block s of draw n is species s's draw, laid out as the sampler
+ * lays it out.  1 <= n_species <= BL_RICHNESS_MAX_SPECIES.  With psi[n][i][s] the float32 bl_deterministic gives at site i for block
+ * s of draw n, bit for bit, the species' presences are independent Bernoulli(psi_s) given the draw and their number is
+ * Poisson-binomial.  In float64, with S = n_species:
+ *   p_s = (double) psi[n][i][s],  q_s = 1.0 - p_s
+ *   pi  = [1, 0, .., 0] (S + 1 entries);  for s = 0 .. S - 1 in ascending order:  pi_new[r] = pi[r] * q_s + pi[r - 1] * p_s  (pi[-1] = 0)
+ *         -- two products and one sum, each rounded once, nothing fused.  A species with p_s = 0 leaves every entry's bits unchanged.
+ *   E[n][i] = sum_s p_s, in ascending s
+ * Per site, over ALL n_draws draws, every sum one float64 accumulator in ascending draw order -- so the result depends neither on the
+ * launch nor on how the draws are chunked -- and nothing of size [n_draws][N] stored:
+ *   site_pmf          [i][r] = (sum_n pi[n][i][r]) / n_draws                                   [N][n_species + 1]
+ *   site_expected_mean[i]    = (sum_n E[n][i]) / n_draws                                       [N]
+ *   site_expected_sd  [i]    = sqrt(sum_n (E[n][i] - mean)^2 / (n_draws - 1)), a second pass; NaN for n_draws == 1      [N]
+ * Per draw and region, the weighted area that holds exactly r species, r = 0 .. S; region, weight and n_regions are bl_regional_totals':
+ *   area_total[n][r][g] = sum_{i in g} weight_i * pi[n][i][r]                                  [n_draws][n_species + 1][n_regions]
+ * Order and workspace are bl_regional_totals': every product in float64, region g's sites in site order cut into runs of 64, the last
+ * filled up with -0.0, a run summed as the tree (x_l + x_{l+32}), then lanes 16, 8, 4, 2, 1 apart, the runs' sums added in run order, no
+ * atomics; region g's rows are a function of its own sites, their weights and the draws, however the draws are chunked, and two calls
+ * return the same bytes.  A region without a site comes back 0.  The device holds one double per (draw of a chunk, row, run of 64) and
+ * per (draw of a chunk, row, region), at most BL_TOTALS_WORKSPACE_BYTES each -- or one draw's rows --, whatever n_draws is; the site
+ * side has no workspace.
+ * float64 on the host, NULL = skip (all four NULL: BL_ERR_INVALID); a skipped output never changes another.  region is read only for
+ * area_total and may be NULL iff area_total is.  Refused with BL_ERR_INVALID, the message holding the offending value: n_species < 1;
+ * n_regions < 1; a label outside -1 .. n_regions - 1; a non-finite weight.  n_species > BL_RICHNESS_MAX_SPECIES: BL_ERR_UNSUPPORTED, the
+ * message names the count and the cap.  Every output is untouched on any refusal.  Serves the occu family -- plain, with a
+ * false-positive rate, with random effects --; every other model and a joint-species handle: BL_ERR_UNSUPPORTED, the message names the
+ * model.  BL_ERR_BUSY while a NUTS launch is in flight on the handle.  Draws must be finite.
+ */
+#define BL_RICHNESS_MAX_SPECIES 32
+int bl_species_richness(bl_dataset *ds, int n_species, int n_draws, const float *draws /* [n_draws][n_species][D] */, int n_regions,
+                        const int32_t *region, const double *weight /* [N], NULL = 1 */, double *site_pmf, double *site_expected_mean,
+                        double *site_expected_sd, double *area_total);
+
+/*
  * Posterior predictive draws of the discrete sites, one per posterior draw -- what
  * numpyro.infer.Predictive(model_fn, posterior_samples)(key, site_covs, obs_covs) samples in
  * biolith/utils/predict.py:66-92 (obs withheld, so no observation is masked):
