@@ -80,6 +80,7 @@ EXPORTS = (
     "bl_score_posterior", "bl_count_posterior", "bl_predict_comb", "bl_deterministic_comb", "bl_predictive_check",
     "bl_predictive_density", "bl_psis_loo", "bl_predictive_check_counts", "bl_site_summary", "bl_regional_totals",
     "bl_site_diagnostics", "bl_response_curves", "bl_trajectory_totals", "bl_species_richness",
+    "bl_residual_moran",
 )
 
 _lib = None
@@ -168,6 +169,8 @@ def load():
         L.bl_response_curves.argtypes = [vp, C.c_int, fp, C.c_int, C.c_int, C.c_int, fp, dp, dp]
         L.bl_trajectory_totals.argtypes = [vp, C.c_int, fp, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_int32), dp] + [dp] * 7
         L.bl_species_richness.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, C.POINTER(C.c_int32), dp, dp, dp, dp, dp]
+        i32p = C.POINTER(C.c_int32)
+        L.bl_residual_moran.argtypes = [vp, C.c_int, fp, C.c_uint64, C.c_uint64, C.c_int32, i32p, i32p, dp, dp, dp, i32p, dp, dp, i32p]
         L.bl_psis_loo.argtypes = [C.c_int, C.c_int, C.c_int64, fp, C.c_int64, dp, dp, dp]
         L.bl_site_posterior.argtypes = [vp, C.c_int, fp, C.c_uint64, fp, fp, C.POINTER(C.c_uint8)]
         L.bl_abundance_posterior.argtypes = [vp, C.c_int, fp, C.c_uint64, fp, fp, fp, C.POINTER(C.c_int32)]

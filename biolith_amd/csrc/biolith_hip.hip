@@ -37,6 +37,7 @@
 #include "response_curves.hpp"
 #include "trajectory_totals.hpp"
 #include "species_richness.hpp"
+#include "residual_moran.hpp"
 
 // ------------------------------------------------------------------ errors ----
 static thread_local std::string g_err;
@@ -2752,6 +2753,93 @@ extern "C" int bl_species_richness(bl_dataset *ds, int n_species, int n_draws, c
     if (rc) return rc;
     for (int k = 0; k < 3; k++)
         if (host[k]) BL_HIP(hipMemcpy(host[k], *dev[k], cells[k] * 8, hipMemcpyDeviceToHost));
+    return BL_OK;
+}
+
+// ---- residual Moran: per draw and period Moran's I of the occupancy and detection residuals and of their replicates over a sparse
+// neighbour graph, and the residuals' means per site, fused ----
+// (BUILDER-DEFINED; the reference ships the residuals alone.)  Kernels: residual_moran.hip.  They read what bl_site_posterior reads (the
+// sign-folded records: the observations and the masks) and what bl_predict reads (the raw observation covariates, up on first use);
+// next to them goes up the graph.  The Moran side's workspace is 32 bytes per (draw of a chunk, period, site); run_over_draws cuts the
+// draws so that it stays within its 256 MB.  The site side is one launch over all the draws when they are up, as bl_species_richness'.
+static_assert(BL_RM_VAL_BYTES == 32, "bl_residual_moran's comment in the header states the record");
+extern "C" int bl_residual_moran(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, uint64_t seed_rep, int32_t nnz,
+                                 const int32_t *nbr_ptr, const int32_t *nbr_idx, const double *nbr_w, double *moran_occ, double *moran_det,
+                                 int32_t *det_sites, double *occ_mean, double *det_mean, int32_t *n_occupied)
+{
+    const bool gather = moran_occ || moran_det, moran = gather || det_sites, site = occ_mean || det_mean || n_occupied;
+    if (n_draws < 1) return bl_fail(BL_ERR_INVALID, "bl_residual_moran: n_draws=%d, at least 1", n_draws);
+    int rc = per_draw_front("bl_residual_moran", ds, n_draws, draws, moran || site, serves_occu,
+                            "occu, with or without false positives / random effects, one species a handle");
+    if (rc) return rc;
+    const int N = ds->dims.n_sites, T = ds->dims.n_periods, J = ds->dims.n_replicates;
+    if (gather) {
+        if (!nbr_ptr || (!nbr_idx && nnz > 0)) return bl_fail(BL_ERR_INVALID, "bl_residual_moran: Moran's I is wanted and the neighbour graph is NULL");
+        if (nnz < 0) return bl_fail(BL_ERR_INVALID, "bl_residual_moran: nnz=%d is negative", (int)nnz);
+        if (nbr_ptr[0] != 0) return bl_fail(BL_ERR_INVALID, "bl_residual_moran: nbr_ptr[0]=%d, not 0", (int)nbr_ptr[0]);
+        for (int i = 0; i < N; i++)
+            if (nbr_ptr[i + 1] < nbr_ptr[i])
+                return bl_fail(BL_ERR_INVALID, "bl_residual_moran: nbr_ptr[%d]=%d below nbr_ptr[%d]=%d", i + 1, (int)nbr_ptr[i + 1], i, (int)nbr_ptr[i]);
+        if (nbr_ptr[N] != nnz) return bl_fail(BL_ERR_INVALID, "bl_residual_moran: nbr_ptr[%d]=%d, not nnz=%d", N, (int)nbr_ptr[N], (int)nnz);
+        for (int i = 0; i < N; i++)
+            for (int e = nbr_ptr[i]; e < nbr_ptr[i + 1]; e++) {
+                if (nbr_idx[e] < 0 || nbr_idx[e] >= N)
+                    return bl_fail(BL_ERR_INVALID, "bl_residual_moran: nbr_idx[%d]=%d outside 0 .. N - 1 = %d", e, (int)nbr_idx[e], N - 1);
+                if (nbr_idx[e] == i) return bl_fail(BL_ERR_INVALID, "bl_residual_moran: nbr_idx[%d]=%d is a self-loop of site %d", e, (int)nbr_idx[e], i);
+                if (nbr_w && !std::isfinite(nbr_w[e])) return bl_fail(BL_ERR_INVALID, "bl_residual_moran: nbr_w[%d]=%g is not finite", e, nbr_w[e]);
+            }
+    }
+    const size_t cells = (size_t)T * N; // per draw
+    if (moran && cells * BL_RM_VAL_BYTES > BL_TOTALS_WORKSPACE_BYTES)
+        return bl_fail(BL_ERR_UNSUPPORTED, "bl_residual_moran: %d periods x %d sites need more than the workspace's %u bytes a draw", T, N,
+                       (unsigned)BL_TOTALS_WORKSPACE_BYTES);
+    if ((rc = upload_once(&ds->d_wraw, ds->h_wraw))) return rc;
+
+    BlResidualMoranParams p{};
+    p.rows = ds->d_rows; p.wraw = ds->d_wraw; p.ns = ds->n_stride; p.N = N; p.T = T; p.J = J; p.Ks = ds->Ks; p.Ko = ds->Ko; p.D = ds->D;
+    p.a = BlSitePostBlock{ds->KS, J, ds->model == 6 ? ds->re.Ko : ds->Ko, ds->KO + 1, ds->Ks + 1}; // (bl_site_posterior's)
+    p.c = draw_coords(ds);
+    p.seed = (unsigned long long)seed; p.seed_rep = (unsigned long long)seed_rep;
+    p.n_draws = n_draws; p.n_waves = (N + 63) / 64;
+    DevScratch scratch;
+    if (gather) {
+        int *d_ptr = nullptr, *d_idx = nullptr;
+        double *d_w = nullptr;
+        BL_HIP(scratch.alloc((void **)&d_ptr, ((size_t)N + 1) * 4));
+        BL_HIP(hipMemcpy(d_ptr, nbr_ptr, ((size_t)N + 1) * 4, hipMemcpyHostToDevice));
+        BL_HIP(scratch.alloc((void **)&d_idx, (size_t)nnz * 4));
+        if (nnz) BL_HIP(hipMemcpy(d_idx, nbr_idx, (size_t)nnz * 4, hipMemcpyHostToDevice));
+        if (nbr_w && nnz) {
+            BL_HIP(scratch.alloc((void **)&d_w, (size_t)nnz * 8));
+            BL_HIP(hipMemcpy(d_w, nbr_w, (size_t)nnz * 8, hipMemcpyHostToDevice));
+        }
+        p.nbr_ptr = d_ptr; p.nbr_idx = d_idx; p.nbr_w = d_w;
+    }
+    void *const host[3] = {occ_mean, det_mean, n_occupied};
+    void **const dev[3] = {(void **)&p.occ_mean, (void **)&p.det_mean, (void **)&p.n_occupied};
+    const size_t bytes[3] = {cells * 8, cells * 8, cells * 4};
+    for (int k = 0; k < 3; k++)
+        if (host[k]) BL_HIP(scratch.alloc(dev[k], bytes[k]));
+    const size_t W = (size_t)p.n_waves, per = moran ? 1 : 0; // (no Moran output: no workspace)
+    const DrawOut outs[] = {{moran_occ, (size_t)T * 16, (void **)&p.moran_occ, false},
+                            {moran_det, (size_t)T * 16, (void **)&p.moran_det, false},
+                            {det_sites, (size_t)T * 8, (void **)&p.det_sites, false},
+                            {nullptr, per * cells * BL_RM_VAL_BYTES, (void **)&p.val, true},
+                            {nullptr, per * T * W * BL_RM_FIELDS * 4 * 8, (void **)&p.part1, true},
+                            {nullptr, per * T * BL_RM_FIELDS * 2 * 8, (void **)&p.stat, true},
+                            {nullptr, (gather ? 1 : 0) * T * W * BL_RM_FIELDS * 3 * 8, (void **)&p.part3, true}};
+    rc = run_over_draws(ds, n_draws, draws, std::max<size_t>(per * cells * BL_RM_VAL_BYTES, (size_t)T * 16), outs,
+                        [&](const float *d_draws, int n0, int n1, int grid_y) {
+        p.draws = d_draws; p.n0 = n0; p.n1 = n1;
+        int e = 0;
+        if (site && n0 == 0) e = bl_launch_residual_moran_site(&p, nullptr);
+        if (!e && moran) e = bl_launch_residual_moran(&p, grid_y, nullptr);
+        if (!e && n1 == n_draws) e = (int)hipStreamSynchronize(nullptr); // the site kernel reads all the draws
+        return (hipError_t)e;
+    });
+    if (rc) return rc;
+    for (int k = 0; k < 3; k++)
+        if (host[k]) BL_HIP(hipMemcpy(host[k], *dev[k], bytes[k], hipMemcpyDeviceToHost));
     return BL_OK;
 }
 

@@ -13,20 +13,11 @@
 
 #include "posterior_math.hpp"
 #include "pred_rng.hpp"
+#include "site_cell.hpp"
 
 namespace {
 
 constexpr float SP_HL2PI = 0.9189385f;
-
-// f = sigmoid(phi): f, 1 - f, log f, log(1 - f)
-__device__ __forceinline__ void sp_rate(float phi, float &f, float &g, float &lf, float &l1f)
-{
-    const float e = bl_exp(-fabsf(phi)), l = post_log1p(e), r = bl_rcp(1.0f + e);
-    f = (phi > 0.0f ? 1.0f : e) * r;
-    g = (phi > 0.0f ? e : 1.0f) * r;
-    lf = fminf(phi, 0.0f) - l;
-    l1f = -fmaxf(phi, 0.0f) - l;
-}
 
 } // namespace
 
@@ -39,15 +30,8 @@ __global__ void bl_site_posterior_kernel(const BlSitePostParams p)
     const int ns = p.ns, N = p.N, T = p.T;
     for (int n = p.n0 + blockIdx.y; n < p.n1; n += gridDim.y) {
         const float *__restrict__ th = p.draws + (size_t)n * p.D;
-        float eta = th[0];
-        for (int k = 0; k < p.Ks; k++) eta = fmaf(rows[(size_t)k * ns + i], th[k + 1], eta);
-        if (p.c.o_u >= 0) eta += th[p.c.o_u + i];
-        const float vi = p.c.o_v >= 0 ? th[p.c.o_v + i] : 0.0f;
-        const float ee = bl_exp(-fabsf(eta)), lop = post_log1p(ee);
-        const float log_psi = fminf(eta, 0.0f) - lop, log_1mpsi = fminf(-eta, 0.0f) - lop;
-        const float psi = (eta > 0.0f ? 1.0f : ee) * bl_rcp(1.0f + ee);
-        // the draw's scalars: what a detection / a non-detection of block a costs at z = 0, the rate that acts at z = 1
-        float f1 = 0.0f, l1f1 = 0.0f, z0_det = POST_LOG_TINY, z0_non = 0.0f;
+        // the draw's scalars for this site (site_cell.hpp); occu_comb's point counts take no false-positive rate of the draw's layout
+        const SiteCellPrior s = sc_prior<!COMB>(rows, ns, i, p.Ks, th, p.c);
         float fc = 0.0f, lgc = 0.0f, lp0 = 0.0f, lq0 = 0.0f, mu0 = 0.0f, mu1 = 0.0f, c0 = 0.0f, c1 = 0.0f, is0 = 0.0f, is1 = 0.0f;
         if constexpr (COMB) {
             float gc, fu, gu, lfc, lfu, lgu;
@@ -58,45 +42,19 @@ __global__ void bl_site_posterior_kernel(const BlSitePostParams p)
             mu0 = th[p.o_x + 2]; mu1 = mu0 + bl_exp(th[p.o_x + 3]);
             c0 = th[p.o_x + 4] + SP_HL2PI; c1 = th[p.o_x + 5] + SP_HL2PI;              // log sigma + log(2 pi) / 2
             is0 = bl_exp(-2.0f * th[p.o_x + 4]); is1 = bl_exp(-2.0f * th[p.o_x + 5]);  // 1 / sigma^2
-        } else if (p.c.fp_mode) {
-            float f, g;
-            sp_rate(th[p.c.o_fp], f, g, z0_det, z0_non);
-            if (p.c.fp_mode == 1) { f1 = f; l1f1 = z0_non; }
         }
         for (int t = 0; t < T; t++) {
-            PostSum a1;
-            a1.add(log_psi);
-            float nd = 0.0f, nn = 0.0f; // unmasked detections / non-detections of block a
-            const float *__restrict__ al = th + p.a.o_al;
-            for (int j = 0; j < p.a.J; j++) {
-                const int v = t * p.a.J + j;
-                const size_t r = (size_t)(p.a.r0 + v * p.a.vw) * ns + i;
-                const float c = rows[r];
-                if (c == 0.0f) continue; // masked
-                float u = c * al[0];
-                for (int k = 1; k <= p.a.K; k++) u = fmaf(rows[r + (size_t)k * ns], al[k], u);
-                if constexpr (!COMB) {
-                    float re = vi;
-                    if (p.c.o_e >= 0) re += th[(size_t)p.c.o_e + (size_t)i * T * p.a.J + v];
-                    u = fmaf(c, re, u);
-                }
-                const float e = bl_exp(-fabsf(u)), lsu = fminf(u, 0.0f) - post_log1p(e); // log sigma(u)
-                if (c > 0.0f) {
-                    nd += 1.0f;
-                    if (f1 > 0.0f) { // log(p + f (1 - p))
-                        const float rop = bl_rcp(1.0f + e);
-                        a1.add(bl_log(fmaf(f1, (u > 0.0f ? e : 1.0f) * rop, (u > 0.0f ? 1.0f : e) * rop)));
-                    } else
-                        a1.add(lsu);
-                } else {
-                    nn += 1.0f;
-                    a1.add(lsu);
-                }
-            }
-            a1.add(nn * l1f1);
-            float B = log_1mpsi + fmaf(nd, z0_det, nn * z0_non);
-            float nobs = nd + nn;
-            if constexpr (COMB) {
+            float l, q;
+            if constexpr (!COMB) {
+                sc_cell(rows, ns, i, T, t, p.a, th, p.c, s, l, q); // (the statement bl_residual_moran's kernels share)
+            } else {
+                PostSum a1;
+                a1.add(s.log_psi);
+                float nd = 0.0f, nn = 0.0f; // unmasked detections / non-detections of block a
+                sc_visits<false>(rows, ns, i, T, t, p.a, th, p.c, s, a1, nd, nn);
+                a1.add(nn * s.l1f1);
+                float B = s.log_1mpsi + fmaf(nd, s.z0_det, nn * s.z0_non);
+                float nobs = nd + nn;
                 float ad = 0.0f, an = 0.0f;
                 const float *__restrict__ aar = th + p.b.o_al;
                 for (int j = 0; j < p.b.J; j++) {
@@ -124,12 +82,8 @@ __global__ void bl_site_posterior_kernel(const BlSitePostParams p)
                 a1.add(fmaf(-0.5f, q1, -sc_n * c1));
                 B += fmaf(ad, lp0, an * lq0) + fmaf(-0.5f, q0, -sc_n * c0);
                 nobs += ad + an + sc_n;
+                sc_conditional(a1.s, B, nobs, s.psi, l, q);
             }
-            const float A = a1.s;
-            const float d = A - B, e = bl_exp(-fabsf(d));
-            float l = fmaxf(A, B) + post_log1p(e);
-            float q = (d > 0.0f ? 1.0f : e) * bl_rcp(1.0f + e);
-            if (nobs == 0.0f) { l = 0.0f; q = psi; } // nothing observed: the cell's likelihood is 1 and the conditional is the prior
             const size_t o = ((size_t)(n - p.n0) * T + t) * N + i;
             if (p.log_lik) p.log_lik[o] = l;
             if (p.z_prob) p.z_prob[o] = q;

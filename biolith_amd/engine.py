@@ -629,6 +629,54 @@ class OccuDataset:
                                                  _dp(w), _dp(pmf), _dp(mean), _dp(sd), _dp(out_area)))
         return pmf, mean, sd, out_area
 
+    def residual_moran(self, draws, graph=None, seed: int = 0, seed_rep: int = 1, moran: bool = True, site: bool = True):
+        """Spatial autocorrelation of the residuals of Wright, Irvine and Higgs (2019) for draws (n, D), fused on the device
+        (BUILDER-DEFINED): ``moran_occ, moran_det, det_sites, occ_mean, det_mean, n_occupied``, ``None`` where not wanted.  The
+        handle carries the observations.  Per draw and period, with ``moran``: ``moran_occ`` (n, T, 2) Moran's I over ``graph`` of
+        the occupancy residual ``z - psi`` -- ``z`` is ``site_posterior``'s for ``seed``, ``psi`` ``deterministic``'s, bit for bit
+        -- and of its replicate, ``predictive``'s ``z`` for ``seed_rep``; ``moran_det`` (n, T, 2) the same of the site-level
+        detection residual, the mean of ``y - prob_detection`` over the cell's seen visits at the sites the draw has occupied,
+        and of its replicate (``predictive``'s ``y`` and ``z``); ``det_sites`` (n, T, 2) int32 the sites in each.  The residual is
+        against ``prob_detection``, as the reference's ``residuals`` forms it, also on a handle with a false-positive rate.
+        ``I`` is NaN where fewer than two sites are in the field, where the weights in it sum to 0 or where its values are all
+        equal.  With ``site``, over all the draws in draw order: ``occ_mean`` (T, N) the mean occupancy residual, ``n_occupied``
+        (T, N) int32 the draws in which the site is in the detection field, ``det_mean`` (T, N) the detection residual's mean over
+        those draws, NaN where there is none.  ``graph`` is CSR ``(indptr, indices, data)``, ``data`` ``None`` = 1, and need not be
+        symmetric; it is read for ``moran`` alone.  Every sum has a fixed order: the same call returns the same bytes
+        (include/biolith_hip.h: bl_residual_moran)."""
+        d = np.asarray(draws, dtype=np.float32)
+        if d.ndim != 2 or d.shape[1] != self.D:
+            raise ValueError(f"residual_moran(): draws must be (n, {self.D}) for this dataset, got shape {d.shape}")
+        d = np.ascontiguousarray(d)
+        n = d.shape[0]
+        if not (moran or site):
+            raise ValueError("residual_moran(): neither Moran's I nor the site outputs are wanted")
+        if n == 0:
+            raise ValueError("residual_moran(): no draws")
+        ptr = idx = w = None
+        nnz = 0
+        if moran:
+            if graph is None:
+                raise ValueError("residual_moran(): Moran's I needs the neighbour graph")
+            ptr = np.ascontiguousarray(np.asarray(graph[0]).reshape(-1), dtype=np.int32)
+            idx = np.ascontiguousarray(np.asarray(graph[1]).reshape(-1), dtype=np.int32)
+            w = None if graph[2] is None else np.ascontiguousarray(np.asarray(graph[2], dtype=np.float64).reshape(-1))
+            if ptr.size != self.N + 1 or (w is not None and w.size != idx.size):
+                raise ValueError(f"residual_moran(): the graph's indptr holds N + 1 = {self.N + 1} entries, its data one per index")
+            nnz = int(idx.size)
+        ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+        m_occ = np.empty((n, self.T, 2)) if moran else None
+        m_det = np.empty((n, self.T, 2)) if moran else None
+        sites = np.empty((n, self.T, 2), dtype=np.int32) if moran else None
+        o_mean = np.empty((self.T, self.N)) if site else None
+        d_mean = np.empty((self.T, self.N)) if site else None
+        n_occ = np.empty((self.T, self.N), dtype=np.int32) if site else None
+        mask = 2 ** 64 - 1
+        _ffi.check(self._lib.bl_residual_moran(self._h, n, _fp(d), C.c_uint64(int(seed) & mask), C.c_uint64(int(seed_rep) & mask), nnz,
+                                               ip(ptr), ip(idx), _dp(w), _dp(m_occ), _dp(m_det), ip(sites), _dp(o_mean), _dp(d_mean),
+                                               ip(n_occ)))
+        return m_occ, m_det, sites, o_mean, d_mean, n_occ
+
     def _per_draw(self, fn, draws, seed, outs, pinned=True):
         """Calls a per-draw entry ``fn(handle, n, draws, seed, *outputs)`` for draws (n, D).  ``outs`` lists (wanted, shape behind
         the draw axis, dtype) per output; returns the arrays, ``None`` where not wanted.  With ``pinned`` the 4-byte outputs come from

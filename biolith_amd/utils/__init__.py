@@ -17,7 +17,8 @@ from .regional_totals import regional_totals
 from .response_curves import response_curves
 from .trajectory_totals import trajectory_totals
 from .species_richness import species_richness
+from .residual_moran import neighbour_graph, residual_moran
 from .counts import conditional_counts
 
-__all__ = ["fit", "FitResult", "predict", "predict_comb", "predictive_check", "predictive_check_counts", "information_criteria", "site_summary", "site_diagnostics", "regional_totals", "response_curves", "trajectory_totals", "species_richness", "conditional_occupancy", "conditional_abundance", "conditional_dynamics", "conditional_scores", "conditional_counts", "loo_marginal", "compare_marginal", "grid_search_priors", "GridSearchResult", "init_to_uniform", "init_to_feasible", "init_to_value",
+__all__ = ["fit", "FitResult", "predict", "predict_comb", "predictive_check", "predictive_check_counts", "information_criteria", "site_summary", "site_diagnostics", "regional_totals", "response_curves", "trajectory_totals", "species_richness", "residual_moran", "neighbour_graph", "conditional_occupancy", "conditional_abundance", "conditional_dynamics", "conditional_scores", "conditional_counts", "loo_marginal", "compare_marginal", "grid_search_priors", "GridSearchResult", "init_to_uniform", "init_to_feasible", "init_to_value",
            "init_to_mean", "init_to_median", "init_to_sample"]

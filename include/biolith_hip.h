@@ -532,6 +532,54 @@ int bl_species_richness(bl_dataset *ds, int n_species, int n_draws, const float 
                         double *site_expected_sd, double *area_total);
 
 /*
+ * Spatial autocorrelation of the residuals: per posterior draw and period, Moran's I of the occupancy and the site-level detection
+ * residuals of Wright, Irvine and Higgs (2019) over a sparse neighbour graph, each next to the same statistic of a replicate drawn from
+ * the model, and the residuals' means over the draws per site, fused -- BUILDER-DEFINED (the reference ships the residuals,
+ * biolith/evaluation/residuals.py, and leaves the statistic to its users, who would form arrays [n_draws][J][T][N] on the host).  ds is
+ * ONE single-species occu handle built WITH the observations, as for bl_site_posterior.  Per draw n, period t, site i, in float64
+ * unless said otherwise:
+ *   psi_i, p_ij   bl_deterministic's float32 psi and prob_detection, bit for bit
+ *   z_i           bl_site_posterior's z for `seed`, bit for bit: the first uniform of the cell's generator against the conditional q
+ *   z'_i, y'_ij   bl_predict's latent state and y for `seed_rep`, bit for bit
+ *   seen          a visit whose record in the handle is unmasked: the observation, the visit's covariates and the site's covariates
+ *                 are all present;  s_it the number of seen visits of the cell,  y_ij the handle's observation
+ * Occupancy residual  o_i = z_i - psi_i, its replicate o'_i = z'_i - psi_i; mask m_i = 1 for every site.
+ * Detection residual  d_i = (sum_{j seen} (y_ij - p_ij)) / s_it, the sum in visit order; mask m_i = [z_i = 1 and s_it > 0].  Its
+ *                     replicate takes y' and z' over the SAME seen visits.  The residual is against prob_detection, as the reference's
+ *                     residuals() forms it, also where the handle has a false-positive rate.
+ * The neighbour graph is CSR: row i holds nbr_idx[e], nbr_w[e] for e = nbr_ptr[i] .. nbr_ptr[i + 1] - 1 (nbr_w NULL = 1); it need not be
+ * symmetric.  Moran's I of a masked field (v, m):
+ *   M = sum_i m_i,  mu = (sum_i m_i v_i) / M,  c_i = v_i - mu
+ *   num = sum_i m_i c_i s_i,  s_i = sum_{e in row i} w_e m_j c_j  (j = nbr_idx[e]; the products w_e c_j summed in CSR order from +0)
+ *   den = sum_i m_i c_i^2,    W = sum_i m_i W_i,  W_i = sum_{e in row i} w_e m_j
+ *   I = (M / W) * num / den, evaluated left to right;  NaN where M < 2, where W == 0, or where the masked v are all equal -- tested as
+ *   max == min, exact and order-free, not as den == 0.
+ * Every product and sum is rounded once, nothing fused.  The sums over sites are bl_regional_totals': the sites in order cut into runs
+ * of 64, the last filled up, a site outside the mask and a filler holding -0.0; a run summed as the tree (x_l + x_{l+32}), then lanes
+ * 16, 8, 4, 2, 1 apart; the runs' sums added in run order.  No atomics: two calls return the same bytes, and a draw's values depend
+ * neither on how the draws are chunked nor on the outputs asked for.
+ *   moran_occ[n][t][0 / 1]  I of (o, 1) / of (o', 1)                                   [n_draws][T][2]
+ *   moran_det[n][t][0 / 1]  I of (d, m) / of (d', m')                                  [n_draws][T][2]
+ *   det_sites[n][t][0 / 1]  M of the detection field / of its replicate                [n_draws][T][2]
+ * Per (period, site), over ALL n_draws draws, one float64 accumulator in ascending draw order:
+ *   occ_mean  [t][i] = (sum_n o_i) / n_draws                                           [T][N]
+ *   n_occupied[t][i] = the draws with m_i = 1 for the detection field                  [T][N]
+ *   det_mean  [t][i] = (sum over those draws of d_i) / n_occupied; NaN where it is 0   [T][N]
+ * NULL = skip (all six NULL: BL_ERR_INVALID); a skipped output never changes another.  The graph is read for moran_occ and moran_det
+ * alone and may be NULL when neither is wanted.  The device holds 32 bytes per (draw of a chunk, period, site) -- the four fields'
+ * values, what the gather reads of a neighbour --, at most BL_TOTALS_WORKSPACE_BYTES, whatever n_draws is; a single draw that needs
+ * more (T N above 2^23): BL_ERR_UNSUPPORTED.  The site side has no workspace.
+ * Refused with BL_ERR_INVALID before anything is launched, the message naming the index and the value: n_draws < 1; a Moran output
+ * wanted with nbr_ptr or nbr_idx NULL; nnz < 0; nbr_ptr[0] != 0; a decreasing nbr_ptr; nbr_ptr[N] != nnz; an index outside 0 .. N - 1;
+ * a self-loop; a non-finite weight.  Serves the one-species handles of bl_dataset_create, _fp, _re and _re_fp; every other model,
+ * occu_comb and joint-species handles included: BL_ERR_UNSUPPORTED, the message names the model.  BL_ERR_BUSY while a NUTS launch is in
+ * flight on the handle.  Every output is untouched on any refusal.  Draws must be finite.
+ */
+int bl_residual_moran(bl_dataset *ds, int n_draws, const float *draws, uint64_t seed, uint64_t seed_rep, int32_t nnz,
+                      const int32_t *nbr_ptr /* [N + 1] */, const int32_t *nbr_idx /* [nnz] */, const double *nbr_w /* [nnz], NULL = 1 */,
+                      double *moran_occ, double *moran_det, int32_t *det_sites, double *occ_mean, double *det_mean, int32_t *n_occupied);
+
+/*
  * Posterior predictive draws of the discrete sites, one per posterior draw -- what
  * numpyro.infer.Predictive(model_fn, posterior_samples)(key, site_covs, obs_covs) samples in
  * biolith/utils/predict.py:66-92 (obs withheld, so no observation is masked):
