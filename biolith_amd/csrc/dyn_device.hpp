@@ -16,7 +16,8 @@
 // Per site pair and lane, everything in registers except 2 T pairs of floats in a lane-private LDS column:
 //   pass 1   per period: a_t = sum_j log sigma(u_j) + ka  (log P(y_t | z_t = 1)), kb_t (log P(y_t | z_t = 0)); the scaled FORWARD
 //            recursion  pi_1 = psi,  phi_t = P(z_t = 1 | y_1..t) = sigmoid(log pi_t + a_t - log(1 - pi_t) - kb_t),
-//            pi_t+1 = phi_t (1 - eps) + (1 - phi_t) gamma;  the log-likelihood is the sum of the normalisers;  (phi_t, pi_t+1) -> LDS;
+//            pi_t+1 = phi_t (1 - eps) + (1 - phi_t) gamma;  the log-likelihood is the sum of the normalisers;  (phi_t, 1 - phi_t) -> LDS
+//            (pi_t+1 and 1 - pi_t+1 are re-formed from them in the backward pass: complement pairs, see bl_sigmoid2_pair);
 //   backward rho_T = phi_T,  xi_t(a, b) = rho_t+1(b) phi_t(a) P(b | a) / pi_t+1(b),  rho_t = xi(1,1) + xi(1,0):
 //            d/d eta_gamma = sum_t xi(0,1) (1 - gamma) - xi(0,0) gamma,  d/d eta_eps = sum_t xi(1,0) (1 - eps) - xi(1,1) eps,
 //            d/d eta_psi = rho_1 - psi;  rho_t -> LDS;
@@ -43,6 +44,19 @@ __device__ __forceinline__ bl_f2 bl_sigmoid2(bl_f2 x)
 {
     const bl_f2 e = bl_exp2_2(__builtin_elementwise_abs(x) * bl2(-BL_LOG2E));
     return bl_sel_pos_one(x, e) * bl_rcp_2(e + bl2(1.0f));
+}
+
+// sigma(x) and its complement 1 - sigma(x) = sigma(-x) from ONE exponential, neither formed as a difference from 1.  Every form below keeps
+// such COMPLEMENT PAIRS -- (psi, 1 - psi), (gamma, 1 - gamma), (eps, 1 - eps), and through the recursions (pi_t, 1 - pi_t), (phi_t, 1 - phi_t),
+// (rho_t, 1 - rho_t) as sums of positive terms: `1.0f - eps` at eps = 1 - 1e-3 is 1e-3 to 6e-5 of itself, and a site that a detection
+// forces occupied pays log(1 - eps) at every transition (measured against the exact fixture, tests/test_gpu_dyn_forms.py: 4.5e-6 of U
+// at T = 16 before, 1e-7 after).
+__device__ __forceinline__ void bl_sigmoid2_pair(bl_f2 x, bl_f2 &s, bl_f2 &ns)
+{
+    const bl_f2 e = bl_exp2_2(__builtin_elementwise_abs(x) * bl2(-BL_LOG2E));
+    const bl_f2 r = bl_rcp_2(e + bl2(1.0f));
+    s = bl_sel_pos_one(x, e) * r;
+    ns = bl_sel_pos_e(x, e) * r;
 }
 
 // Accumulates over this thread's site PAIRS m = ct, ct + CT, ...: ll, gb[b][k] = d ll / d (block b's coefficient k), ga[k] = d ll / d alpha_k
@@ -86,15 +100,15 @@ __device__ __forceinline__ void bl_eval_sites_dyn(int ct, int pstride, int cnt, 
             e_gam = bl_fma2(x[k], bl2(bgam[k + 1]), e_gam);
             e_eps = bl_fma2(x[k], bl2(beps[k + 1]), e_eps);
         }
-        const bl_f2 gam = bl_sigmoid2(e_gam), eps = bl_sigmoid2(e_eps);
+        bl_f2 gam, ngam, eps, neps;                                              // (ngam = 1 - gamma, neps = 1 - eps: complement pairs)
+        bl_sigmoid2_pair(e_gam, gam, ngam); bl_sigmoid2_pair(e_eps, eps, neps);
         // log psi, log(1 - psi) in their exact forms (a site far in a tail of psi keeps its relative precision)
         const bl_f2 ee = bl_exp2_2(__builtin_elementwise_abs(e_psi) * bl2(-BL_LOG2E)), op = ee + bl2(1.0f);
         const bl_f2 lop = bl_log2_2(op) * bl2(BL_LN2);
         const bl_f2 psi = bl_sel_pos_one(e_psi, ee) * bl_rcp_2(op);
         bl_f2 lpi = __builtin_elementwise_min(e_psi, bl2(0.0f)) - lop;           // log pi_1
         bl_f2 l1m = __builtin_elementwise_min(-e_psi, bl2(0.0f)) - lop;          // log(1 - pi_1)
-        const bl_f2 stay = bl2(1.0f) - eps - gam;                                // pi_t+1 = gamma + phi_t (1 - eps - gamma)
-        bl_f2 lsite = bl2(0.0f), phi = bl2(0.0f);
+        bl_f2 lsite = bl2(0.0f), phi = bl2(0.0f), nphi = bl2(0.0f);
         // ---- pass 1: the periods' visit sums (this lane's share of the periods), handed to the group through LDS ----
         for (int t = sub; t < T; t += G) {
             const float2 *pp = rec + XQ + t * pb;
@@ -122,29 +136,33 @@ __device__ __forceinline__ void bl_eval_sites_dyn(int ct, int pstride, int cnt, 
             const bl_f2 d = A - B;
             const bl_f2 e_d = bl_exp2_2(__builtin_elementwise_abs(d) * bl2(-BL_LOG2E)), op_d = e_d + bl2(1.0f);
             lsite += bl_fma2(bl_log2_2(op_d), bl2(BL_LN2), __builtin_elementwise_max(A, B));
-            phi = bl_sel_pos_one(d, e_d) * bl_rcp_2(op_d);     // P(z_t = 1 | y_1..t)
-            const bl_f2 pin = bl_fma2(phi, stay, gam);         // P(z_t+1 = 1 | y_1..t)
+            const bl_f2 r_d = bl_rcp_2(op_d);
+            phi = bl_sel_pos_one(d, e_d) * r_d;                // P(z_t = 1 | y_1..t)
+            nphi = bl_sel_pos_e(d, e_d) * r_d;                 // P(z_t = 0 | y_1..t)
+            const bl_f2 pin = bl_fma2(phi, neps, nphi * gam);  // P(z_t+1 = 1 | y_1..t)
+            const bl_f2 qin = bl_fma2(phi, eps, nphi * ngam);  // P(z_t+1 = 0 | y_1..t)
             col[(2 * t) * CT] = make_float2(phi.x, phi.y);
-            col[(2 * t + 1) * CT] = make_float2(pin.x, pin.y);
+            col[(2 * t + 1) * CT] = make_float2(nphi.x, nphi.y);
             lpi = bl_log2_2(pin) * bl2(BL_LN2);
-            l1m = bl_log2_2(bl2(1.0f) - pin) * bl2(BL_LN2);
+            l1m = bl_log2_2(qin) * bl2(BL_LN2);
         }
         // ---- backward: the smoothed marginals rho_t (left in LDS over phi_t) and the transitions' gradient sums ----
-        bl_f2 rho = phi, d_gam = bl2(0.0f), d_eps = bl2(0.0f);
+        bl_f2 rho = phi, nrho = nphi, d_gam = bl2(0.0f), d_eps = bl2(0.0f);
         for (int t = T - 2; t >= 0; t--) {
-            const float2 f_ = col[(2 * t) * CT], p_ = col[(2 * t + 1) * CT];
-            const bl_f2 f = bl_f2{f_.x, f_.y}, p1 = bl_f2{p_.x, p_.y};
+            const float2 f_ = col[(2 * t) * CT], n_ = col[(2 * t + 1) * CT];
+            const bl_f2 f = bl_f2{f_.x, f_.y}, nf = bl_f2{n_.x, n_.y};
+            const bl_f2 p1 = bl_fma2(f, neps, nf * gam), q1 = bl_fma2(f, eps, nf * ngam); // pi_t+1, 1 - pi_t+1 (as the forward pass formed them)
             // w1 = rho / pi_t+1, w0 = (1 - rho) / (1 - pi_t+1)   (0 where the denominator is: that state cannot be reached)
-            const bl_f2 r1 = bl_rcp_2(p1), r0 = bl_rcp_2(bl2(1.0f) - p1);
+            const bl_f2 r1 = bl_rcp_2(p1), r0 = bl_rcp_2(q1);
             const bl_f2 w1 = bl_f2{p1.x > 0.0f ? rho.x * r1.x : 0.0f, p1.y > 0.0f ? rho.y * r1.y : 0.0f};
-            const bl_f2 w0 = bl_f2{p1.x < 1.0f ? (1.0f - rho.x) * r0.x : 0.0f, p1.y < 1.0f ? (1.0f - rho.y) * r0.y : 0.0f};
-            const bl_f2 nf = bl2(1.0f) - f;
-            const bl_f2 xi11 = w1 * f * (bl2(1.0f) - eps), xi01 = w1 * nf * gam;
-            const bl_f2 xi10 = w0 * f * eps, xi00 = w0 * nf * (bl2(1.0f) - gam);
-            d_gam += xi01 * (bl2(1.0f) - gam) - xi00 * gam;
-            d_eps += xi10 * (bl2(1.0f) - eps) - xi11 * eps;
+            const bl_f2 w0 = bl_f2{q1.x > 0.0f ? nrho.x * r0.x : 0.0f, q1.y > 0.0f ? nrho.y * r0.y : 0.0f};
+            const bl_f2 xi11 = w1 * f * neps, xi01 = w1 * nf * gam;
+            const bl_f2 xi10 = w0 * f * eps, xi00 = w0 * nf * ngam;
+            d_gam += xi01 * ngam - xi00 * gam;
+            d_eps += xi10 * neps - xi11 * eps;
             col[(2 * (t + 1)) * CT] = make_float2(rho.x, rho.y);
             rho = xi11 + xi10;
+            nrho = xi01 + xi00;
         }
         // ---- pass 2: d/d alpha = sum_t rho_t sum_j sigma(-u_j) (c, c w)_j   (this lane's share of the periods) ----
         for (int t = sub; t < T; t += G) {
@@ -236,8 +254,8 @@ __device__ __forceinline__ void bl_eval_sites_dyn_scaled(int ct, int pstride, in
             e_gam = bl_fma2(x[k], bl2(bgam[k + 1]), e_gam);
             e_eps = bl_fma2(x[k], bl2(beps[k + 1]), e_eps);
         }
-        const bl_f2 gam = bl_sigmoid2(e_gam), eps = bl_sigmoid2(e_eps), psi = bl_sigmoid2(e_psi);
-        const bl_f2 stay = bl2(1.0f) - eps - gam;                                // pi_t+1 = gamma + phi_t (1 - eps - gamma)
+        bl_f2 gam, ngam, eps, neps, psi, npsi;                                   // (n..: the complements 1 - gamma, 1 - eps, 1 - psi)
+        bl_sigmoid2_pair(e_gam, gam, ngam); bl_sigmoid2_pair(e_eps, eps, neps); bl_sigmoid2_pair(e_psi, psi, npsi);
         // ---- this lane's periods t = sub, sub + G: visits (log-likelihood and gradient sums at once), scaled likelihoods -> LDS ----
         bl_f2 gt[2][KO + 1], own_m[2], own_c[2], own_rho[2];
 #pragma unroll
@@ -270,54 +288,62 @@ __device__ __forceinline__ void bl_eval_sites_dyn_scaled(int ct, int pstride, in
         }
         if (G > 1) bl_wave_lds_fence();
         // ---- the scaled forward recursion (every lane of the group, all periods) ----
-        // One step's dependent chain is  c = E0 + pi (E1 - E0)  ->  1 / c  ->  phi = (pi E1) / c  ->  pi' = gamma + phi stay ; the next
+        // One step's dependent chain is  c = pi E1 + (1 - pi) E0  ->  1 / c  ->  (phi, 1 - phi) = (pi E1, (1 - pi) E0) / c  ->
+        // (pi', 1 - pi') = (phi (1 - eps) + (1 - phi) gamma,  phi eps + (1 - phi)(1 - gamma)): positive terms only ; the next
         // step's scaled likelihoods are loaded a step ahead (the compiler will not move an LDS load across the stores of the loop, so the
         // order is written out here: without it every step paid an LDS round trip on top of its chain).
-        bl_f2 pi = psi, phi = bl2(0.0f);
+        bl_f2 pi = psi, qi = npsi, phi = bl2(0.0f), nphi = bl2(0.0f);
         float2 e1n = ecol[0], e0n = ecol[nslots];
         for (int t = 0; t < T; t++) {
             const bl_f2 E1 = bl_f2{e1n.x, e1n.y}, E0 = bl_f2{e0n.x, e0n.y};
             const int tn = min(t + 1, T - 1);
             e1n = ecol[(2 * tn) * nslots]; e0n = ecol[(2 * tn + 1) * nslots];
-            const bl_f2 a1 = pi * E1;
-            const bl_f2 c = __builtin_elementwise_max(bl_fma2(pi, E1 - E0, E0), bl2(1e-37f)); // P(y_t | y_1..t-1) / e^m_t  (> 0 unless pi left (0, 1) in f32)
-            phi = a1 * bl_rcp_2(c);                            // P(z_t = 1 | y_1..t)
-            const bl_f2 pin = bl_fma2(phi, stay, gam);         // P(z_t+1 = 1 | y_1..t)
+            const bl_f2 a1 = pi * E1, a0 = qi * E0;
+            const bl_f2 c = __builtin_elementwise_max(a1 + a0, bl2(1e-37f)); // P(y_t | y_1..t-1) / e^m_t
+            const bl_f2 rc = bl_rcp_2(c);
+            phi = a1 * rc;                                     // P(z_t = 1 | y_1..t)
+            nphi = a0 * rc;                                    // P(z_t = 0 | y_1..t)
             col[(2 * t) * CT] = make_float2(phi.x, phi.y);
-            col[(2 * t + 1) * CT] = make_float2(pin.x, pin.y);
+            col[(2 * t + 1) * CT] = make_float2(nphi.x, nphi.y);
             if (t == sub) own_c[0] = c;
             if (t == sub + G) own_c[1] = c;
-            pi = pin;
+            pi = bl_fma2(phi, neps, nphi * gam);               // P(z_t+1 = 1 | y_1..t)
+            qi = bl_fma2(phi, eps, nphi * ngam);               // P(z_t+1 = 0 | y_1..t)
         }
         // ---- backward: the smoothed marginals rho_t and the transitions' gradient sums ----
-        // With r1 = 1 / pi_t+1, r0 = 1 / (1 - pi_t+1) (0 where that state cannot be reached) the pairwise marginals are
-        //   xi(1,1) = rho r1 f (1 - eps),  xi(0,1) = rho r1 (1 - f) gamma,  xi(1,0) = (1 - rho) r0 f eps,  xi(0,0) = (1 - rho) r0 (1 - f)(1 - gamma),
-        // so  rho_t = xi(1,1) + xi(1,0) = A0 + rho (A1 - A0)  with A1 = r1 f (1 - eps), A0 = r0 f eps -- ONE fma on the dependent chain --
-        // and with  Dl = rho r1 - (1 - rho) r0 :  d/d eta_gamma += (1 - f) gamma (1 - gamma) Dl,  d/d eta_eps -= f eps (1 - eps) Dl
-        // (the first form's xi(0,1)(1 - gamma) - xi(0,0) gamma and xi(1,0)(1 - eps) - xi(1,1) eps, factored).  Everything but the fma hangs
-        // off (f, pi_t+1), which are loaded a step ahead.
-        bl_f2 rho = phi, d_gam = bl2(0.0f), d_eps = bl2(0.0f);
+        // With r1 = 1 / pi_t+1, r0 = 1 / (1 - pi_t+1) (0 where that state cannot be reached; both re-formed from (f, 1 - f) as the forward
+        // pass formed them) the pairwise marginals are
+        //   xi(1,1) = rho B11,  xi(0,1) = rho B01,  xi(1,0) = (1 - rho) B10,  xi(0,0) = (1 - rho) B00,
+        //   B11 = r1 f (1 - eps),  B01 = r1 (1 - f) gamma,  B10 = r0 f eps,  B00 = r0 (1 - f)(1 - gamma),
+        // so  (rho_t, 1 - rho_t) = (rho B11 + (1 - rho) B10,  rho B01 + (1 - rho) B00)  -- a multiply and an fma on the dependent chain, the
+        // pair carried as sums of positive terms -- and with  Dl = rho r1 - (1 - rho) r0 :  d/d eta_gamma += (1 - f) gamma (1 - gamma) Dl,
+        // d/d eta_eps -= f eps (1 - eps) Dl  (the first form's xi(0,1)(1 - gamma) - xi(0,0) gamma and xi(1,0)(1 - eps) - xi(1,1) eps, factored).
+        // The B's hang off (f, 1 - f), which are loaded a step ahead.
+        bl_f2 rho = phi, nrho = nphi, d_gam = bl2(0.0f), d_eps = bl2(0.0f);
         if (T - 1 == sub) own_rho[0] = rho;
         if (T - 1 == sub + G) own_rho[1] = rho;
-        const bl_f2 g1g = gam * (bl2(1.0f) - gam), e1e = eps * (bl2(1.0f) - eps);
+        const bl_f2 g1g = gam * ngam, e1e = eps * neps;
         {
             // (volatile LDS-address-space loads: the loop has no store, so the compiler is otherwise free to sink the "a step ahead" loads
             // to right in front of their use -- it did: `ds_read2st64_b64 ... s_waitcnt lgkmcnt(0)` at the head of every step)
             typedef __attribute__((address_space(3))) const volatile bl_f2 BlLdsV2;
             const int t0 = max(T - 2, 0);
-            bl_f2 fn = *(BlLdsV2 *)&col[(2 * t0) * CT], pn = *(BlLdsV2 *)&col[(2 * t0 + 1) * CT];
+            bl_f2 fn = *(BlLdsV2 *)&col[(2 * t0) * CT], pn = *(BlLdsV2 *)&col[(2 * t0 + 1) * CT]; // (f, 1 - f) of the step ahead
             for (int t = T - 2; t >= 0; t--) {
-                const bl_f2 f = fn, p1 = pn;
+                const bl_f2 f = fn, nf = pn;
                 const int tp = max(t - 1, 0);
                 fn = *(BlLdsV2 *)&col[(2 * tp) * CT]; pn = *(BlLdsV2 *)&col[(2 * tp + 1) * CT];
-                const bl_f2 q1 = bl_rcp_2(p1), q0 = bl_rcp_2(bl2(1.0f) - p1);
+                const bl_f2 p1 = bl_fma2(f, neps, nf * gam), p0 = bl_fma2(f, eps, nf * ngam); // pi_t+1, 1 - pi_t+1
+                const bl_f2 q1 = bl_rcp_2(p1), q0 = bl_rcp_2(p0);
                 const bl_f2 r1 = bl_f2{p1.x > 0.0f ? q1.x : 0.0f, p1.y > 0.0f ? q1.y : 0.0f};
-                const bl_f2 r0 = bl_f2{p1.x < 1.0f ? q0.x : 0.0f, p1.y < 1.0f ? q0.y : 0.0f};
-                const bl_f2 A1 = r1 * f * (bl2(1.0f) - eps), A0 = r0 * f * eps;
-                const bl_f2 Dl = bl_fma2(rho, r1 + r0, -r0);
-                d_gam = bl_fma2((bl2(1.0f) - f) * g1g, Dl, d_gam);
+                const bl_f2 r0 = bl_f2{p0.x > 0.0f ? q0.x : 0.0f, p0.y > 0.0f ? q0.y : 0.0f};
+                const bl_f2 B11 = r1 * f * neps, B10 = r0 * f * eps, B01 = r1 * nf * gam, B00 = r0 * nf * ngam;
+                const bl_f2 Dl = bl_fma2(rho, r1, -(nrho * r0));
+                d_gam = bl_fma2(nf * g1g, Dl, d_gam);
                 d_eps = bl_fma2(f * e1e, -Dl, d_eps);
-                rho = bl_fma2(rho, A1 - A0, A0);
+                const bl_f2 rho_n = bl_fma2(rho, B11, nrho * B10);
+                nrho = bl_fma2(rho, B01, nrho * B00);
+                rho = rho_n;
                 if (t == sub) own_rho[0] = rho;
                 if (t == sub + G) own_rho[1] = rho;
             }
@@ -442,7 +468,8 @@ __device__ __forceinline__ void bl_eval_sites_dyn_scan(int ct, int pstride, int 
             e_gam = bl_fma2(x[k], bl2(bgam[k + 1]), e_gam);
             e_eps = bl_fma2(x[k], bl2(beps[k + 1]), e_eps);
         }
-        const bl_f2 gam = bl_sigmoid2(e_gam), eps = bl_sigmoid2(e_eps), psi = bl_sigmoid2(e_psi);
+        bl_f2 gam, ngam, eps, neps, psi, npsi;         // (n..: the complements 1 - gamma, 1 - eps, 1 - psi)
+        bl_sigmoid2_pair(e_gam, gam, ngam); bl_sigmoid2_pair(e_eps, eps, neps); bl_sigmoid2_pair(e_psi, psi, npsi);
         // ---- this lane's period: visits (log-likelihood and gradient sums at once), scaled likelihoods ----
         bl_f2 gt[KO + 1];
 #pragma unroll
@@ -465,8 +492,8 @@ __device__ __forceinline__ void bl_eval_sites_dyn_scan(int ct, int pstride, int 
         const bl_f2 E1 = bl_exp2_2((a - mm) * bl2(BL_LOG2E)), E0 = bl_exp2_2((kb - mm) * bl2(BL_LOG2E));
         // ---- this period's matrix: X_0 = diag(L_0), X_t = A diag(L_t) ----
         BlM22 X;
-        X.a = is_first ? E0 : (bl2(1.0f) - gam) * E0; X.b = is_first ? bl2(0.0f) : gam * E1;
-        X.c = is_first ? bl2(0.0f) : eps * E0;        X.d = is_first ? E1 : (bl2(1.0f) - eps) * E1;
+        X.a = is_first ? E0 : ngam * E0;       X.b = is_first ? bl2(0.0f) : gam * E1;
+        X.c = is_first ? bl2(0.0f) : eps * E0; X.d = is_first ? E1 : neps * E1;
         // ---- inclusive prefix products P_t = X_0 ... X_t and suffix products S_t = X_t ... X_T-1 over the group's lanes ----
         BlM22 P = X, S = X;
         bl_f2 eP = bl2(0.0f);                          // P's true value is P x 2^eP
@@ -490,14 +517,14 @@ __device__ __forceinline__ void bl_eval_sites_dyn_scan(int ct, int pstride, int 
         BlM22 Qo; // what this lane hands to the left: X_t (.) beta_t, column-wise
         Qo.a = X.a * be0; Qo.b = X.b * be1; Qo.c = X.c * be0; Qo.d = X.d * be1;
         const BlM22 Q = bl_m22_dpp_or_identity<0x101>(Qo, !is_last); // Q_t+1 (the last lane: the identity -- beta = 1, no transition)
-        const bl_f2 al0 = bl_fma2(psi, P.c, (bl2(1.0f) - psi) * P.a), al1 = bl_fma2(psi, P.d, (bl2(1.0f) - psi) * P.b);
+        const bl_f2 al0 = bl_fma2(psi, P.c, npsi * P.a), al1 = bl_fma2(psi, P.d, npsi * P.b);
         const bl_f2 Z = __builtin_elementwise_max(bl_fma2(al1, Q.c + Q.d, al0 * (Q.a + Q.b)), bl2(1e-37f));
         const bl_f2 rz = bl_rcp_2(Z);
         const bl_f2 rho = al1 * (Q.c + Q.d) * rz;      // P(z_t = 1 | y)
         const bl_f2 t0 = al0 * rz, t1 = al1 * rz;
         const bl_f2 nx = is_last ? bl2(0.0f) : vm;     // (the last period starts no transition)
-        const bl_f2 d_gam = (t0 * Q.b * (bl2(1.0f) - gam) - t0 * Q.a * gam) * nx;   // xi(0,1)(1 - gamma) - xi(0,0) gamma
-        const bl_f2 d_eps = (t1 * Q.c * (bl2(1.0f) - eps) - t1 * Q.d * eps) * nx;   // xi(1,0)(1 - eps) - xi(1,1) eps
+        const bl_f2 d_gam = (t0 * Q.b * ngam - t0 * Q.a * gam) * nx;   // xi(0,1)(1 - gamma) - xi(0,0) gamma
+        const bl_f2 d_eps = (t1 * Q.c * neps - t1 * Q.d * eps) * nx;   // xi(1,0)(1 - eps) - xi(1,1) eps
         const bl_f2 d_psi = is_first ? (rho - psi) * vm : bl2(0.0f);
         // ---- log-likelihood: every lane its period's scale m_t, the last lane log(alpha_T-1 . 1) and the prefix's power of two ----
         bl_f2 lown = mm;

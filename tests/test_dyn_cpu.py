@@ -36,6 +36,24 @@ def test_forward_recursion_equals_brute_force_over_paths(T):
         assert abs(U + oracle.literal_log_joint_dyn(th, X, W, Y, (0.2, 1.5), (-0.1, 0.8))) < 1e-10 * max(1.0, abs(U))
 
 
+def test_forward_recursion_equals_brute_force_on_the_data_edges():
+    """T = 8 on the data-edge dataset of the exact fixture (tests/dyn_cases.py: seasons and sites without data, a site detected at every
+    visit, one never, one whose detections alternate), at |theta| <= 2 -- where the float64 literal is trustworthy.  The fixture's own
+    U at the bulk row ties the literal, the oracle and the mpmath statement (test_dyn_exact_cpu.py) to one another."""
+    import dyn_cases
+
+    X, W, Y, theta, kw, U_exact, _ = dyn_cases.load_exact("t8")
+    assert W.shape[1] == 8 and not kw
+    od = oracle.OracleData(X, W, Y, model="occu_dyn")
+    bulk = theta[0].astype(np.float64)
+    assert np.abs(bulk).max() <= 2.0
+    rng = np.random.default_rng(8)
+    for th in [bulk, *rng.uniform(-2, 2, size=(2, od.D))]:
+        U, _ = od.potential_grad(th)
+        assert abs(U + oracle.literal_log_joint_dyn(th, X, W, Y)) < 1e-10 * max(1.0, abs(U))
+    assert abs(U_exact[0] + oracle.literal_log_joint_dyn(bulk, X, W, Y)) < 1e-10 * max(1.0, abs(U_exact[0]))
+
+
 def test_gradient_equals_central_differences():
     rng = np.random.default_rng(3)
     X, W, Y = _data(rng, N=40, T=6, J=4)

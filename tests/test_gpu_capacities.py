@@ -1,7 +1,7 @@
 """Every padded covariate-capacity pair is its own kernel instantiation (register allocation, unrolling and record
 strides differ).  The model-specific test files concentrate on the capacities their fixtures have; this one runs the
-extra-coordinate and count models at the largest capacity they are built for, and at two lopsided ones: K1 parity
-through the C-ABI against the oracle, and the same first NUTS trees."""
+extra-coordinate and count models and the dynamic model at the largest capacity they are built for, and at two lopsided
+ones: K1 parity through the C-ABI against the oracle, and the same first NUTS trees."""
 import numpy as np
 import pytest
 
@@ -52,6 +52,33 @@ def test_model_capacities(model, ks, ko):
     assert np.max(np.abs(Gg - Go)) <= 2e-5 * tol * np.max(np.abs(Go))
     o = oracle.nuts_run(od, 0, 4, num_chains=2, seed=3)
     r = ds.nuts(num_warmup=0, num_samples=4, num_chains=2, seed=3)
+    assert np.array_equal(o["num_steps"][:, :3], r.num_steps[:, :3]), (o["num_steps"], r.num_steps)
+    assert np.allclose(o["draws"][:, 0], r.draws[:, 0], atol=2e-3)
+
+
+@pytest.mark.parametrize("ks,ko", [(4, 4), (8, 16), (3, 1)])
+def test_dyn_capacities(ks, ko):
+    """occu_dyn (builder-defined, no reference counterpart) above 3 + 3 covariates: (8, 16) is the fullest instantiation it is built for
+    (BL_DYN_MAX_KS); a wave's 3 (KS + 1) + KO + 2 partial sums take the butterfly at all three (21, 45 and 15 of them), where the
+    3 + 3 of the other dynamic tests (17) take the reduce-scatter (bl_wave_partials_dyn)."""
+    rng = np.random.default_rng(100 * ks + 10 * ko + 8)
+    N, T, J = 333, 3, 4
+    scale = 0.2 if ks + ko > 8 else 0.4
+    X = rng.normal(size=(N, ks)) * scale
+    W = rng.normal(size=(N, T, J, ko)) * scale
+    Y = (rng.uniform(size=(1, N, T, J)) < 0.3) * 1.0
+    Y[rng.uniform(size=Y.shape) < 0.08] = np.nan
+    od, ds = oracle.OracleData(X, W, Y, model="occu_dyn"), OccuDataset(X, W, Y, model="occu_dyn")
+    assert ds.D == od.D == 3 * (ks + 1) + ko + 1
+    th = rng.uniform(-0.7, 0.7, size=(3, od.D)).astype(np.float32).astype(np.float64)
+    Uo, Go = od.potential_grad(th)
+    Ug, Gg = ds.logp_grad(th)
+    assert np.max(np.abs(Ug - Uo) / np.abs(Uo)) <= 1e-6, (Ug, Uo)                       # (the dynamic kernel's own bounds: test_gpu_dyn.py)
+    assert np.max(np.abs(Gg - Go)) <= 1e-5 * np.max(np.abs(Go))
+    init = rng.uniform(-0.3, 0.3, size=(2, od.D)).astype(np.float32).astype(np.float64)
+    o = oracle.nuts_run(od, 0, 4, num_chains=2, seed=3, init=init)
+    r = ds.nuts(num_warmup=0, num_samples=4, num_chains=2, seed=3, init_theta=init)
+    assert r.kernel_name.startswith(f"bl_nuts_kernel<{ks}, {ko}, true, 8, "), r.kernel_name
     assert np.array_equal(o["num_steps"][:, :3], r.num_steps[:, :3]), (o["num_steps"], r.num_steps)
     assert np.allclose(o["draws"][:, 0], r.draws[:, 0], atol=2e-3)
 

@@ -1,7 +1,8 @@
 """Randomised shapes through every model of the engine: potential and gradient over all coordinates against the CPU oracle.
 Sixty seeded draws of (model, sites, periods, visits, covariate counts, missing-data pattern, priors) -- the ragged corners the
 hand-written cases do not name: one site, one visit, no covariates on one side or both, sites or periods without data, slices that
-do not fill a workgroup, 5-16 covariates (the capacity-8 / 16 kernels)."""
+do not fill a workgroup, 5-16 covariates (the capacity-8 / 16 kernels).  occu_dyn (builder-defined, no reference counterpart) has a seed
+range of its own behind the first sixty-six, so that every earlier seed keeps its model and its draws."""
 import numpy as np
 import pytest
 
@@ -10,17 +11,21 @@ from biolith_amd.engine import OccuDataset
 
 pytestmark = pytest.mark.gpu
 
-MODELS = ["occu", "occu_fp_c", "occu_fp_u", "occu_rn", "occu_cop", "occu_cop_fp", "nmixture", "occu_re_s", "occu_re_o", "occu_re_so", "occu_cs"]
+MODELS = ["occu", "occu_fp_c", "occu_fp_u", "occu_rn", "occu_cop", "occu_cop_fp", "nmixture", "occu_re_s", "occu_re_o", "occu_re_so", "occu_cs", "occu_dyn"]
+CYCLED = MODELS.index("occu_dyn")   # seeds 0 .. 65 go round the models before it, as they always have;
+DYN_SEEDS = range(66, 78)           # occu_dyn: twelve seeds of its own
 JOINT = ["occu", "occu_fp_c", "occu_fp_u", "occu_re_s", "occu_re_so"]   # several species under one chain
 
 
 def _draw(seed):
     rng = np.random.default_rng(1000 + seed)
-    model = MODELS[seed % len(MODELS)]
+    model = "occu_dyn" if seed in DYN_SEEDS else MODELS[seed % CYCLED]
     N = int(rng.choice([1, 2, 3, 17, 64, 65, 130, 333, 700]))
-    T = int(rng.choice([1, 1, 2, 3]))
+    T = int(rng.choice([1, 2, 3, 5, 8, 12] if model == "occu_dyn" else [1, 1, 2, 3]))
     J = int(rng.choice([1, 2, 5, 9]))
     Ks = int(rng.choice([0, 1, 3, 4, 5, 8, 11, 16]))
+    if model == "occu_dyn":
+        Ks = min(Ks, 8)   # (three coefficient blocks: BL_DYN_MAX_KS)
     Ko = int(rng.choice([0, 1, 2, 4, 6, 8, 16]))
     X = rng.normal(size=(N, Ks)).astype(np.float32) * 0.7
     W = rng.normal(size=(N, T, J, Ko)).astype(np.float32) * 0.7
@@ -41,6 +46,8 @@ def _draw(seed):
             kw = dict(model="occu_fp", fp_mode="constant" if model.endswith("c") else "unoccupied", prior_fp=(2.0, 6.0))
         elif model == "occu_rn":
             kw = dict(model="occu_rn", max_abundance=int(rng.choice([5, 30, 100])))
+        elif model == "occu_dyn":
+            kw = dict(model="occu_dyn")
         elif model.startswith("occu_re"):
             kw = dict(model="occu_re", site_random_effects="s" in model.split("_")[2], obs_random_effects="o" in model.split("_")[2],
                       prior_site_re_sd=0.8, prior_obs_re_sd=1.2)
@@ -60,7 +67,7 @@ def _draw(seed):
     return rng, model, X, W, Y, priors, kw
 
 
-@pytest.mark.parametrize("seed", range(66))
+@pytest.mark.parametrize("seed", [*range(66), *DYN_SEEDS])
 def test_random_shape_potential_and_gradient(seed):
     rng, model, X, W, Y, priors, kw = _draw(seed)
     od = oracle.OracleData(X, W, Y[0], *priors, **kw)
@@ -78,7 +85,7 @@ def test_random_shape_potential_and_gradient(seed):
     assert np.max(np.abs(Gg - Go)) <= 5e-5 * max(np.max(np.abs(Go)), 1.0), (model, X.shape, W.shape, np.max(np.abs(Gg - Go)), np.max(np.abs(Go)))
 
 
-@pytest.mark.parametrize("seed", range(33))
+@pytest.mark.parametrize("seed", [*range(33), *DYN_SEEDS[:6]])
 def test_random_shape_first_trees(seed):
     """The same random shapes through the sampler: the first two trees of two chains equal the oracle's (same xoshiro streams),
     the first draws agree to float32 accuracy; on one workgroup per chain and on the engine's own choice."""
