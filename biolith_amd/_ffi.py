@@ -80,7 +80,7 @@ EXPORTS = (
     "bl_score_posterior", "bl_count_posterior", "bl_predict_comb", "bl_deterministic_comb", "bl_predictive_check",
     "bl_predictive_density", "bl_psis_loo", "bl_predictive_check_counts", "bl_site_summary", "bl_regional_totals",
     "bl_site_diagnostics", "bl_response_curves", "bl_trajectory_totals", "bl_species_richness",
-    "bl_residual_moran",
+    "bl_residual_moran", "bl_nuts_record_bytes",
 )
 
 _lib = None
@@ -151,6 +151,8 @@ def load():
         if hasattr(L, "bl_nuts_env_overrides"):   # (absent from libraries built before round 6: tools/ A/B them by name, BIOLITH_HIP_LIB)
             L.bl_nuts_env_overrides.argtypes = [vp, C.c_char_p, C.c_int]
             L.bl_env_overrides.argtypes = [C.c_char_p, C.c_int]
+        if hasattr(L, "bl_nuts_record_bytes"):    # (absent from libraries built before the compact records, loaded by name for an A/B)
+            L.bl_nuts_record_bytes.argtypes = [vp, ip]
         L.bl_nuts_debug_counters.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
         L.bl_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
         L.bl_host_free.argtypes = [C.c_void_p]
@@ -190,7 +192,7 @@ def load():
         L.bl_result_block_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         L.bl_gather_unpack.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(bl_nuts_output)]
         for name in EXPORTS:
-            if name != "bl_last_error" and (hasattr(L, name) or name not in ("bl_nuts_env_overrides", "bl_env_overrides")):
+            if name != "bl_last_error" and (hasattr(L, name) or name not in ("bl_nuts_env_overrides", "bl_env_overrides", "bl_nuts_record_bytes")):
                 getattr(L, name).restype = C.c_int
         if L.bl_abi_version() != 1:
             raise RuntimeError("libbiolith_hip.so ABI version mismatch")

@@ -2140,7 +2140,10 @@ extern "C" int bl_nuts_launch(bl_dataset *ds, const bl_nuts_config *cfg, void *s
     int pitch = nvp; // granules between workgroup records
     { const char *e = bl_env(BL_ENV_PITCH); if (e && atoi(e) >= nvp && atoi(e) <= 4096) pitch = atoi(e); }
     pitch += pitch & 1; // (even: the paired records' 16-byte loads stay aligned -- nuts_kernel.hpp BL_POLL_PAIRS)
-    const size_t xb = align256((size_t)C * BL_XCHG_SLOTS * k * pitch * 8);
+    // (which record form runs is the dispatcher's choice -- BIOLITH_HIP_GENERAL=1 among its inputs -- so the allocation and the clear
+    // cover both: the pitched records and the compact form's fixed 2 KB slots, nuts_kernel.hpp BL_POLL_COMPACT)
+    const size_t xb_pitched = (size_t)C * BL_XCHG_SLOTS * k * pitch * 8, xb_compact = (size_t)C * BL_XCHG_SLOTS * BL_COMPACT_SLOT_BYTES;
+    const size_t xb = align256(xb_pitched > xb_compact ? xb_pitched : xb_compact);
     if (xb > ds->xchg_bytes) {
         if (ds->d_xchg) hipFree(ds->d_xchg);
         ds->d_xchg = nullptr; ds->xchg_bytes = 0;
@@ -2397,6 +2400,21 @@ extern "C" int bl_nuts_geometry(bl_dataset *ds, int *wgs_per_chain, int *threads
             for (int v : loc) *chains_on_l2_local_exchange += v;
         }
     }
+    return BL_OK;
+}
+
+// Bytes of one workgroup's exchange record in the last FINISHED launch: 64 where the kernel that ran laid out compact records (it says
+// so itself, in the status block's second word), else granules per record x 8 (128, 256 or 512); 0 for the random-effects samplers,
+// whose exchange is their own.
+extern "C" int bl_nuts_record_bytes(bl_dataset *ds, int *record_bytes)
+{
+    if (!ds || !record_bytes) return bl_fail(BL_ERR_INVALID, "NULL argument");
+    if (!ds->have_run || ds->in_flight) return bl_fail(BL_ERR_BUSY, "no finished NUTS launch");
+    int rc = set_device(ds);
+    if (rc) return rc;
+    int said = 0;
+    if (ds->model != 6) BL_HIP(hipMemcpy(&said, ds->d_status + 1, 4, hipMemcpyDeviceToHost));
+    *record_bytes = said > 0 ? said : ds->nvp * 8;
     return BL_OK;
 }
 

@@ -29,7 +29,8 @@
 //     the lean kernels of <= 8 coefficients lay a record out in 16-byte PAIRS of granules and poll it
 //     with four 16-byte sc1 loads per round instead of eight 8-byte ones, then swap the halves back
 //     into the same lanes and the same order of the sums (BL_POLL_PAIRS, below; what it measured:
-//     profiles/NOTES.md, profiles/poll_pairs/);
+//     profiles/NOTES.md, profiles/poll_pairs/); the plain model's among them halve the record once more -- 8 granules, the log-lik
+//     and the rare words in the tags' spare 16 bits, two loads per round (BL_POLL_COMPACT, below; profiles/record_compaction/);
 //   * the control wave (lane d = dimension d) then writes the SPECULATIVE next position -- the next
 //     leaf of the subtree or the first leaf of the next doubling, a few FMAs from the gathered
 //     gradient -- and releases the compute waves; NumPyro's per-leaf decisions (finish the
@@ -105,7 +106,7 @@ struct BlNutsCold {
     float *step_size;              // [C]
     float *inv_mass;               // [C][D]
     long long *nleap;              // [C][2]
-    int *status;                   // [1]
+    int *status;                   // [4]: the run's status; bytes of a workgroup's exchange record where the kernel says so (compact records: 64)
     int *xcd_local;                // [C] 1 if the chain ran on the L2-local exchange
     long long *dbg;                // [BL_DBG_SLOTS] phase cycle counters (diagnostic BL_STAMPS builds only); from 32: chain 0's site-evaluation
                                    // cycles per compute wave, [workgroup][wave] at 8 per workgroup; from 544: the tick behind a
@@ -141,7 +142,7 @@ struct BlNutsParams {
     int sp_lds;                    // floats between two species' record regions in LDS
     unsigned spin_limit;           // bound of an exchange's wait in MICROSECONDS of wall time (a peer that is late -- late-resident,
                                    // descheduled by a co-tenant or a profiler -- is not an error for a while; one that vanished is)
-    unsigned long long *xchg;      // [C][BL_XCHG_SLOTS][k][pitch] granules, zeroed before every launch
+    unsigned long long *xchg;      // [C][BL_XCHG_SLOTS][k][pitch] granules ([C][BL_XCHG_SLOTS][2 KB] for compact records), zeroed before every launch
     const BlNutsCold *cold;
 };
 
@@ -290,6 +291,38 @@ struct BlSpinBound {
 #ifndef BL_POLL_REFILL
 #define BL_POLL_REFILL 1
 #endif
+// Compact records (the lean PLAIN-model kernels of <= 8 coefficients and more than one workgroup per chain: MODEL 0, one pair per lane
+// and lane groups alike): a record is 8 granules (64 bytes), not 16, and a poll round is TWO 16-byte sc1 loads per lane, not four.  A
+// granule is still ONE aligned 8-byte store by one lane: the low dword is the value (gradient component g < D, else 0), the high dword
+// is {payload << 16 | epoch & 0xFFFF}.  The 16 payload bits carry what the paired form spends granules 8-11 on:
+//   granule 0: log-lik bits 15:0        granule 1: log-lik bits 31:16        granule 2: the abort word (member 0, every 256th epoch)
+//   granule 3: the XCC id at epoch 1    granule 4: its square at epoch 1     (small integers: the census k sum(x^2) == (sum x)^2 is exact)
+// A 16-bit tag suffices: slot epoch & 3 is rewritten by every member at every fourth epoch and one lane's stores to one address are
+// ordered, so a reader polling for epoch e can only meet e, that member's last use of the slot (e - 4) or the launch's cleared word;
+// (e - 4) & 0xFFFF != e & 0xFFFF always, and the cleared tag 0 is only met at e <= 4, where e & 0xFFFF = e != 0.
+// Layout (transposed pairs): the 16-byte unit (sub, qp, d) at byte 16 ((sub 4 + qp) 8 + d) of a slot holds granule d of record
+// 4 (2 qp) + sub in its low half and of record 4 (2 qp + 1) + sub in its high half -- two workgroups' 8-byte stores side by side; a slot
+// is 2 KB for any k <= 32 (bl_compact_off).  The poller's lane (h = lane >> 5, sub = (lane >> 3) & 3, d = lane & 7) loads the units
+// (sub, 2 h + j, d), j = 0, 1: eight neighbouring lanes read one 128-byte line, and a round touches half the lines of the paired form.
+// A half whose record is >= k is never written: its lane leaves it out of the tag test by a launch constant (cmask); a load none of
+// whose lanes has a real record (load 1 at k <= 8) is skipped wave-uniformly.  Behind a complete round the lanes d = 1 put the log-lik
+// of their four records together from the tags of lanes d = 0 and d = 1 (one DPP shift and one and-or per record), and four
+// v_permlane32_swap -- as many as the paired form -- hand lanes 0-31 the values of q = 4 ... 7 from lanes 32-63 while, in the register
+// that goes up, lanes 32-63 receive the log-lik of q = 0 ... 3: every lane then runs the SAME f64 chain acc += pval[q] * value(4 q + sub),
+// q = 0 ... 7 from 0.0, and the sub rows fold as (s0 + s1) + (s2 + s3), so the sums are the paired form's bit for bit.  The gradient
+// totals end in lanes 0-7, the log-lik total in lane 33 (BL_XL(D), whatever D); the abort word is read from lane 2's tag and the census
+// is summed from the tags of lanes d = 3, 4 at epoch 1 (integers; no f64 chain runs over them).  The Royle-Nichols kernels (MODEL 1) keep
+// the paired form: they sit at the 256-register budget and were not measured with this one (profiles/NOTES.md).  0: the paired form
+// everywhere (A/B); publisher, poller and host follow the one switch.
+#ifndef BL_POLL_COMPACT
+#define BL_POLL_COMPACT 1
+#endif
+#define BL_COMPACT_SLOT_BYTES 2048u
+// byte offset within a slot of granule d of workgroup record w (w < 32, d < 8)
+__host__ __device__ __forceinline__ constexpr unsigned bl_compact_off(int w, int d)
+{
+    return 16u * (unsigned)((((w & 3) * 4 + (w >> 3)) * 8) + d) + 8u * (unsigned)((w >> 2) & 1);
+}
 __host__ __device__ __forceinline__ constexpr int bl_pair_pos(int v) { return v < 8 ? 2 * v : 2 * (v - 8) + 1; }
 __host__ __device__ __forceinline__ constexpr int bl_pair_lane(int v) { return v < 8 ? v : 24 + v; }
 typedef unsigned BlU4 __attribute__((ext_vector_type(4)));
@@ -448,7 +481,11 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
     // tags and are ignored in the sum, so a round needs no predication)
     const int nvp = SMALL_D_NVP(LEAN, MODEL, KS, KO) ? 16 : p.nvp, G = 64 / nvp; // (<= 8 coefficients: D + 4 <= 16 granules, a compile-time fact when lean)
     const int c_idx = lane & (nvp - 1), sub = lane / nvp;
-    const unsigned rec_bytes = (unsigned)(p.k * p.pitch * 8);
+    // paired records (BL_POLL_PAIRS): the 16-byte loads of this lane, and after the round's swaps the records 4 q + (lane >> 3 & 3);
+    // compact records (BL_POLL_COMPACT): the plain model's, two loads per round and a fixed 2 KB slot
+    constexpr bool PAIRS = BL_POLL_PAIRS && SMALL_D_NVP(LEAN, MODEL, KS, KO) && multi_wg;
+    constexpr bool COMPACT = BL_POLL_COMPACT && PAIRS && MODEL == 0;
+    const unsigned rec_bytes = COMPACT ? BL_COMPACT_SLOT_BYTES : (unsigned)(p.k * p.pitch * 8); // (bytes of one slot)
     const unsigned char *xbase = reinterpret_cast<const unsigned char *>(p.xchg) + (size_t)chain * BL_XCHG_SLOTS * rec_bytes;
     unsigned poff[8];
     float pval[8]; // 1 if that load is a real (unclamped) record of this lane
@@ -460,12 +497,23 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
     }
     const int nq = (p.k + G - 1) / G; // loads per round actually needed (<= 8 when k <= 8 G)
     const bool one_batch = LEAN || p.k <= 8 * G;
-    // paired records (BL_POLL_PAIRS): the 16-byte loads of this lane, and after the round's swaps the records 4 q + (lane >> 3 & 3)
-    constexpr bool PAIRS = BL_POLL_PAIRS && SMALL_D_NVP(LEAN, MODEL, KS, KO) && multi_wg;
     unsigned ppoff[4] = {0u, 0u, 0u, 0u};
-    // (behind the exchange's fold the total of granule v -- D ... D + 3: log-lik, abort flag, census words -- is read from lane XL(v))
-#define BL_XL(v) (PAIRS ? bl_pair_lane(v) : (v))
-    if constexpr (PAIRS) {
+    // compact records: bits 15:0 set where the low half of this lane's load j is a real record's granule, bits 31:16 where the high half
+    // is (else 0: never written, never tagged)
+    unsigned cmask[2] = {0u, 0u};
+    // (behind the exchange's fold the total of granule v -- D ... D + 3: log-lik, abort flag, census words -- is read from lane XL(v);
+    // compact records: only the log-lik has a total in `acc`, in lane 33 -- the abort word and the census come from the tags)
+#define BL_XL(v) (COMPACT ? 33 : PAIRS ? bl_pair_lane(v) : (v))
+    if constexpr (COMPACT) {
+        const int psub = (lane >> 3) & 3, ph = lane >> 5;
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            ppoff[j] = bl_compact_off(4 * (2 * (2 * ph + j)) + psub, lane & 7);
+            cmask[j] = ((4 * (2 * (2 * ph + j)) + psub < p.k) ? 0xFFFFu : 0u) | ((4 * (2 * (2 * ph + j) + 1) + psub < p.k) ? 0xFFFF0000u : 0u);
+        }
+#pragma unroll
+        for (int q = 0; q < 8; q++) pval[q] = (4 * q + psub < p.k) ? 1.0f : 0.0f;
+    } else if constexpr (PAIRS) {
         const int psub = (lane >> 3) & 3;
 #pragma unroll
         for (int q = 0; q < 4; q++) {
@@ -645,6 +693,7 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
     // Result of the last exchange, waiting for its decisions (made while the compute waves already
     // evaluate the position those decisions are EXPECTED to choose -- see "speculative position" below).
     bool have_pending = false, p_timed_out = false;
+    bool p_abort = false; // (compact records: the abort word of the gathered evaluation, read from its tag)
     double p_acc = 0.0;                 // lane d: d log-lik / d theta_d summed over the chain's workgroups; lane D: log-lik
     float p_cg = 0.f, p_pe2 = 0.f;      // gradient of the potential / twice the prior energy at the evaluated position
     float cz_spec = 0.f;                // position written to LDS for the evaluation in flight
@@ -691,6 +740,15 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
             else v[q] = BlU4{0u, ep, 0u, ep};
         }
     };
+    // compact records: two loads; load 1 has no real record in any lane at k <= 8 and is skipped (its masks are 0 in every lane)
+    auto poll_issue_compact = [&](BlU4 (&v)[4], unsigned ep) {
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(xbase), (short)0, (int)(BL_XCHG_SLOTS * BL_COMPACT_SLOT_BYTES), 0x00020000);
+        const int soff = __builtin_amdgcn_readfirstlane((int)((ep & (BL_XCHG_SLOTS - 1u)) * BL_COMPACT_SLOT_BYTES));
+        asm volatile("" ::: "memory"); // (compiler only: every round loads anew)
+        v[0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)ppoff[0], soff, 16); // (aux 16: sc1)
+        if (p.k > 8) v[1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)ppoff[1], soff, 16);
+        else v[1] = BlU4{0u, 0u, 0u, 0u};
+    };
     auto poll_issue_one = [&](unsigned long long (&v)[8], unsigned ep) {
         const unsigned char *rb = xbase + (ep & (BL_XCHG_SLOTS - 1u)) * rec_bytes;
 #pragma unroll
@@ -714,7 +772,7 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
         const double acc = p_acc;
         const float cg = p_cg, pe2 = p_pe2;
         const double ll_tot = bl_readlane_d(acc, BL_XL(D));
-        const bool abort_req = bl_readlane_d(acc, BL_XL(D + 1)) != 0.0;
+        const bool abort_req = COMPACT ? p_abort : (bl_readlane_d(acc, BL_XL(D + 1)) != 0.0);
         flag = 0;
         if (p_timed_out) flag = 4;     // BL_ERR_TIMEOUT
         else if (abort_req) flag = 5;  // BL_ERR_ABORTED
@@ -866,6 +924,7 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
                 cold->nleap[chain * 2 + 0] = ss->nleap_w;
                 cold->nleap[chain * 2 + 1] = ss->nleap_s;
                 cold->xcd_local[chain] = local ? 1 : 0;
+                if constexpr (COMPACT) cold->status[1] = 64; // (bytes of a workgroup's record as this kernel lays it out: bl_nuts_record_bytes)
             }
         }
     };
@@ -945,6 +1004,42 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
 #pragma unroll
                     for (int w = 0; w < CW; w++) comp += part_all ? (float)part[w * part_rs + sp * BL_SP_PART(KS, KO)] : 0.0f;
                 }
+                if constexpr (COMPACT) {
+                    // Compact record (BL_POLL_COMPACT): lanes 0-7 store {value, payload << 16 | tag}.  The log-lik (lane D of `comp`) goes
+                    // to the payloads of lanes 0 and 1 by one cross-lane read; abort word and census are formed in lanes 2-4 under the
+                    // same rare wave-uniform conditions as in the other forms.  Nothing here is carried across the loop.
+                    const unsigned llb = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(comp), D);
+                    unsigned pay = lane == 0 ? llb << 16 : (lane == 1 ? (llb & 0xFFFF0000u) : 0u);
+                    if (lane >= D) comp = 0.0f;
+                    if constexpr (ABORT_DEFER) {
+                        if (lane == 2 && member == 0 && (epoch_c & 255u) == BL_ABORT_LAG + 1u)
+                            pay = (*(__attribute__((address_space(3))) const volatile int *)(sh_flag + 2) != 0) ? 0x10000u : 0u;
+                    } else {
+                        // (one wave-wide read of the one word, made uniform: read under `lane == 2` the fullest forms -- 8 visits,
+                        // 4 detection covariates -- came out with up to 10 more VGPRs than with the paired records)
+                        if (member == 0 && (epoch_c & 255u) == 0u) {
+                            const unsigned abw = (unsigned)__builtin_amdgcn_readfirstlane(__hip_atomic_load(cold->abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+                            if (lane == 2) pay = abw != 0u ? 0x10000u : 0u;
+                        }
+                    }
+                    if (epoch_c == 1u) { // placement census, as below: the XCC id (< 16) and its square, small integers
+                        const unsigned xcc = bl_xcc_id();
+                        if (lane == 3) pay = xcc << 16;
+                        if (lane == 4) pay = (xcc * xcc) << 16;
+                    }
+                    // (16-bit tag: a reader of slot epoch & 3 can meet only epoch, epoch - 4 or the cleared word -- see BL_POLL_COMPACT)
+                    const unsigned hi = pay | (epoch_c & 0xFFFFu);
+                    const unsigned char *rbase = xbase + (epoch_c & (BL_XCHG_SLOTS - 1u)) * BL_COMPACT_SLOT_BYTES;
+                    const unsigned long long granule = ((unsigned long long)hi << 32) | __float_as_uint(comp);
+                    if (lane < 8) {
+                        int lane_o = lane; // (an opaque copy, as below: the address is formed here, not carried across the loop)
+                        asm volatile("" : "+v"(lane_o));
+                        const unsigned store_off = bl_compact_off(member, 0) + 16u * (unsigned)(lane_o & 7);
+                        unsigned long long *dst = reinterpret_cast<unsigned long long *>(const_cast<unsigned char *>(rbase) + store_off);
+                        if (local_c) __hip_atomic_store(dst, granule, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        else __hip_atomic_store(dst, granule, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                } else {
                 if (lane > D) comp = 0.0f;
                 if constexpr (ABORT_DEFER) { // the word that the sampling wave set behind the last evaluation's publish (below)
                     if (lane == D + 1 && member == 0 && (epoch_c & 255u) == BL_ABORT_LAG + 1u)
@@ -972,6 +1067,7 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
                         __hip_atomic_store(dst, granule, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     else         // write-through: visible to any XCD
                         __hip_atomic_store(dst, granule, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
                 }
             }
             }
@@ -1046,7 +1142,8 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
             if (early) {
                 for (int z = 0; z < p.first_delay; z++) __builtin_amdgcn_s_sleep(1);
                 BL_STAMP_ROUND0
-                if (PAIRS) poll_issue_pairs(pv, epoch + 1u);
+                if (COMPACT) poll_issue_compact(pv, epoch + 1u);
+                else if (PAIRS) poll_issue_pairs(pv, epoch + 1u);
                 else poll_issue_one(ov, epoch + 1u);
                 BL_STAMP(6)
             }
@@ -1121,6 +1218,7 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
             if (!early)
                 for (int z = 0; z < p.first_delay; z++) __builtin_amdgcn_s_sleep(1);
             double acc = 0.0;
+            double cen_sx = 0.0, cen_sxx = 0.0; // (compact records: the census sums, formed at epoch 1 only)
             bool timed_out = false;
             if (!multi_wg) {
                 // ONE workgroup per chain (round 4; small problems -- simulate()'s defaults, the size of the reference's own tests): there is
@@ -1145,6 +1243,72 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
                         comp = (__hip_atomic_load(cold->abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) ? 1.0f : 0.0f;
                 }
                 acc = (double)comp;
+            } else if (COMPACT) {
+                // compact records (see BL_POLL_COMPACT): two 16-byte sc1 loads per lane and round; the first round may already be in
+                // flight (BL_POLL_EARLY), a retry reloads only the loads whose real tags missed (BL_POLL_REFILL)
+                const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(xbase), (short)0, (int)(BL_XCHG_SLOTS * BL_COMPACT_SLOT_BYTES), 0x00020000);
+                const int soff = __builtin_amdgcn_readfirstlane((int)((epoch & (BL_XCHG_SLOTS - 1u)) * BL_COMPACT_SLOT_BYTES));
+                BlSpinBound bound;
+                if (!early) {
+                    BL_STAMP_ROUND0
+                    poll_issue_compact(pv, epoch);
+                }
+                while (true) {
+                    // (the tag is the low 16 bits of a granule's high dword: both tags of a load side by side in one word -- v_perm_b32 --
+                    // against the epoch's low half twice, under the lane's mask of real halves)
+                    const unsigned ep2 = (epoch & 0xFFFFu) * 0x10001u;
+                    unsigned badq[2];
+#pragma unroll
+                    for (int j = 0; j < 2; j++) badq[j] = (__builtin_amdgcn_perm(pv[j].w, pv[j].y, 0x05040100u) ^ ep2) & cmask[j];
+                    const bool all_in = __all((badq[0] | badq[1]) == 0u);
+                    BL_STAMP_ROUND1
+                    if (all_in) break;
+                    if (bound.expired(p.spin_limit)) { timed_out = true; break; }
+                    if (!local)
+                        for (int z = 0; z < p.poll_sleep; z++) __builtin_amdgcn_s_sleep(1);
+                    BL_STAMP_ROUND0
+                    if constexpr (POLL_REFILL) {
+                        asm volatile("" ::: "memory"); // (compiler only: a retry loads anew)
+#pragma unroll
+                        for (int j = 0; j < 2; j++) {
+                            // (the lanes' predicate is the ballot; the skipped load's masks are 0, it never misses)
+                            if (badq[j] != 0u) pv[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)ppoff[j], soff, 16);
+                        }
+                    } else {
+                        poll_issue_compact(pv, epoch);
+                    }
+                }
+                BL_COUNT_SPINS(bound.spins)
+                // the rare words, from the tags' payloads: the abort word is member 0's granule 2 (lane 2, load 0, low half) ...
+                p_abort = ((unsigned)__builtin_amdgcn_readlane((int)pv[0].y, 2) >> 16) != 0u;
+                if (epoch == 1u && p.allow_local) { // ... and the census: the records' XCC ids in the lanes d = 3, their squares in d = 4
+                    float xs = 0.0f;
+#pragma unroll
+                    for (int j = 0; j < 2; j++)
+                        xs += ((cmask[j] & 0xFFFFu) ? (float)(pv[j].y >> 16) : 0.0f) + ((cmask[j] >> 16) ? (float)(pv[j].w >> 16) : 0.0f);
+                    cen_sx = (double)bl_wave_sum((lane & 7) == 3 ? xs : 0.0f);  // (integers <= 32 x 225: exact in f32 in any order)
+                    cen_sxx = (double)bl_wave_sum((lane & 7) == 4 ? xs : 0.0f);
+                }
+                // lanes d = 1: the log-lik of record q, bits 31:16 from the lane's own tag and bits 15:0 from lane d = 0's (row_shr:1)
+                unsigned cval[4], cll[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const unsigned hi = (i & 1) ? pv[i >> 1].w : pv[i >> 1].y;
+                    cval[i] = (i & 1) ? pv[i >> 1].z : pv[i >> 1].x;
+                    cll[i] = (hi & 0xFFFF0000u) | ((unsigned)__builtin_amdgcn_update_dpp(0, (int)hi, 0x111, 0xF, 0xF, false) >> 16);
+                }
+                // lanes 0-31 hold q = 0 ... 3, lanes 32-63 q = 4 ... 7.  swap(value, log-lik): r[0] = {values of q = i | the low lanes'
+                // log-lik of q = i}, r[1] = {the high lanes' values of q = 4 + i | log-lik of q = 4 + i} -- lanes 0-31 sum the granules
+                // 0-7 of the records 4 q + sub, lanes 32-63 with d = 1 their log-lik, by the same instructions in the same order
+                unsigned cup[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const auto r = __builtin_amdgcn_permlane32_swap(cval[i], cll[i], false, false);
+                    acc += (double)(pval[i] * __uint_as_float(r[0]));
+                    cup[i] = r[1];
+                }
+#pragma unroll
+                for (int i = 0; i < 4; i++) acc += (double)(pval[4 + i] * __uint_as_float(cup[i]));
             } else if (PAIRS && (POLL_EARLY || POLL_REFILL)) {
                 // paired records, the first round already in flight (BL_POLL_EARLY) and retries that reload only what is missing
                 // (BL_POLL_REFILL): the first wait for a load stands HERE, behind the barrier, in front of the tag check
@@ -1344,7 +1508,7 @@ __global__ void __launch_bounds__(64 * (CW + 1)) bl_nuts_kernel(const BlNutsPara
             }
             BL_STAMP(3)
             if (epoch == 1u && p.allow_local) {
-                const double sx = bl_readlane_d(acc, BL_XL(D + 2)), sxx = bl_readlane_d(acc, BL_XL(D + 3));
+                const double sx = COMPACT ? cen_sx : bl_readlane_d(acc, BL_XL(D + 2)), sxx = COMPACT ? cen_sxx : bl_readlane_d(acc, BL_XL(D + 3));
                 local = ((double)p.k * sxx == sx * sx); // exact: small integers
                 if (lane == 0) sh_flag[1] = local ? 1 : 0; // (the compute waves' stores from the next evaluation on)
             }

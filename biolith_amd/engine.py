@@ -107,6 +107,7 @@ class NutsResult:
     lane_group: tuple = (1, 1)    # lanes that shared one site pair: (period lanes, visit lanes); (1, 1) = one pair per lane
     kernel_name: str = ""         # the sampler instantiation that ran, as rocprofv3 names it
     env_overrides: str = ""       # BIOLITH_HIP_* knobs set at the launch ("" = none: the engine's own geometry and kernel form)
+    record_bytes: int = 0         # bytes of a workgroup's exchange record: 64 = compact records, 128 / 256 / 512 = 16 / 32 / 64 granules
 
 
 class OccuDataset:
@@ -371,6 +372,14 @@ class OccuDataset:
         _ffi.check(self._lib.bl_nuts_env_overrides(self._h, buf, 512))
         return buf.value.decode()
 
+    def record_bytes(self) -> int:
+        """Bytes of one workgroup's exchange record in the last finished launch (bl_nuts_record_bytes; 0: the library has no such call)."""
+        if not hasattr(self._lib, "bl_nuts_record_bytes"):   # (a library built before the compact records, loaded by name for an A/B)
+            return 0
+        n = C.c_int(0)
+        _ffi.check(self._lib.bl_nuts_record_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
     def elapsed_ms(self) -> float:
         ms = C.c_float(0)
         _ffi.check(self._lib.bl_nuts_elapsed_ms(self._h, C.byref(ms)))
@@ -410,7 +419,8 @@ class OccuDataset:
         return NutsResult(a["draws"], a["diverging"].astype(bool), a["num_steps"], a["accept_prob"], a["potential_energy"],
                           a["step_size"], a["inv_mass"], a["n_leapfrog"], self.elapsed_ms(),
                           k.value, lds.value, bool(staged.value & 1), loc.value, thr.value, staged.value >> 1,
-                          lane_group=(int(gt.value), int(gj.value)), kernel_name=self._kernel_name(), env_overrides=self.env_overrides())
+                          lane_group=(int(gt.value), int(gj.value)), kernel_name=self._kernel_name(), env_overrides=self.env_overrides(),
+                          record_bytes=self.record_bytes())
 
     def fetch(self) -> NutsResult:
         Cn, S = self._shape

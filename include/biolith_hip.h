@@ -301,6 +301,9 @@ int bl_nuts_device_draws(bl_dataset *ds, void **dev_ptr, size_t *bytes);
  * vectors lived in LDS (0 none, 1 the five of the leaf in flight, 2 every vector a leapfrog touches). */
 int bl_nuts_geometry(bl_dataset *ds, int *wgs_per_chain, int *threads_per_wg, int *lds_bytes, int *lds_staged,
                      int *chains_on_l2_local_exchange);
+/* Bytes of one workgroup's exchange record in the last finished launch: 64 = the compact records of the lean plain-model kernels
+ * (8 granules, the ninth value and the rare words in the tags' spare bits), 128 / 256 / 512 = 16 / 32 / 64 granules of 8 bytes. */
+int bl_nuts_record_bytes(bl_dataset *ds, int *record_bytes);
 
 /* Lanes that shared one site pair in the last launch (1, 1 = one pair per lane): period_lanes split the pair's periods, visit_lanes
  * the visits of a period -- the layout SURVEY.md 7.1 asks for when a site has many visits (simulate() defaults: 52 per site,
